@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py — the Markov-propagation hot path on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps 40 --warmup 3
+    python bench.py --gpus 1 --steps 40 --warmup 3                         (the headline alone)
+    python bench.py --gpus 1 --steps 40 --warmup 3 --full                  (+ checks, CPU baseline, whitened loop, end to end)
+    python bench.py --gpus 1 --steps 40 --warmup 3 --dump-outputs DIR      (+ the last timed step's iterate as DIR/*.npy)
     python bench.py --gpus N --steps K --warmup W          (WORLD_SIZE unset: bench.py launches its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -12,18 +14,24 @@ embed_full) on the synthetic power-law graph |V| = 10M, |E| = nnz ~ 200M, d = 25
 config 3).  The graph, X and the CSR are resident in HBM before the timed region.  Total work is
 fixed as N grows ("strong" scaling: BASELINE.json quotes the same graph at 1/2/4/8 GPUs).
 
+A plain run does what the headline needs and nothing else: it builds the graph, places the iterates, warms up, times K steps
+(`ms_per_step`, `value`, and `roofline` from the HIP events recorded inside those steps) and prints the line.  --dump-outputs DIR
+then writes the iterate the last timed step computed (iterate.npy: float32, a fixed seeded sample of its rows when it is larger
+than 48 MiB; iterate_rows.npy: the rows' indices) — the graph, the hashes and E_0 are seeded, so two builds started with the same
+arguments can be compared output for output.  Everything below that is marked --full is measured or checked only with --full.
+
 N > 1 (csrc/sharded.hip through cleora_amd/sharded.py; kernels AND collectives go through the C ABI — RCCL is bound directly in
 csrc/comm.hip; torch.distributed/gloo is only the launcher: it distributes the RCCL id and reduces the
-timings).  BOTH partitions are measured, W + K iterations each, and reported in `partitions`:
+timings).  The row partition is the headline; --full measures BOTH partitions, W + K iterations each, and reports them in `partitions`:
   row     north_star's layout: row blocks of the CSR, full replicas of X, in-place all-gather of the
           10 GB iterate per iteration over xGMI (block k's gather overlaps block k+1's SpMM);
   column  each rank owns d/N columns of X and the whole CSR; the only collective per iteration is an
           all-reduce of the n row sums-of-squares.
 `value` is the ROW partition's (north_star's layout) for every N; the column partition is reported beside it.
-Before the big graph is built, every partition runs one iteration on a 100k-row graph and is compared with the same
+With --full, before the big graph is built, every partition runs one iteration on a 100k-row graph and is compared with the same
 iteration computed by the rank alone (`selftest`; a broken collective costs seconds, not the run).
 
-N = 1 additionally reports `whitened` — the default pycleora.embed() loop (SpMM + L2, then
+N = 1 with --full additionally reports `whitened` — the default pycleora.embed() loop (SpMM + L2, then
 whiten_embeddings: pycleora/__init__.py:109-117,130-164) with per-kernel milliseconds from HIP events and
 MFMA roofline fractions for the Gram and projection kernels —, `checks` (one GPU iteration against one
 oracle iteration on the same graph and X: every row compared) and `cpu_baseline` (the oracle's
@@ -845,11 +853,15 @@ def run_partition(part, args, g, hashes, deg, dev, rank, world, comm, launcher, 
     avg_ms = (rows_ms + other_ms) / max(calls, 1)
     avg_bytes = sum(launch_bytes) / len(launch_bytes)
     achieved = avg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    finite, sumsq = finite_and_row_sumsq(a, n)
-    if part == "column" and world > 1:
-        comm.allreduce(sumsq)
-        torch.cuda.synchronize()
-    norm_err = float((sumsq.sqrt() - 1).abs().max())
+    if args.dump_outputs and rank == 0 and part == args.headline:
+        dump_outputs(args.dump_outputs, a, n)          # before anything below iterates again
+    checks = {}
+    if args.full:
+        finite, sumsq = finite_and_row_sumsq(a, n)
+        if part == "column" and world > 1:
+            comm.allreduce(sumsq)
+            torch.cuda.synchronize()
+        checks = {"finite": finite, "max_abs_row_norm_minus_1": float((sumsq.sqrt() - 1).abs().max())}
     hot_rows = int(blocks[0].info().hot_rows)      # gather cache policy (cleora_graph_set_hot_cache), 0 = inactive
     g_lanes = max(8, min(64, 1 << (max(dl // 4, 1) - 1).bit_length()))
     n_long = sum(int(blk.info().n_hub_rows) for blk in blocks)
@@ -872,13 +884,25 @@ def run_partition(part, args, g, hashes, deg, dev, rank, world, comm, launcher, 
                      "frac_of_measured_copy_ceiling_6290": achieved / 6290.0,
                      # SURVEY.md §8(d) secondary model: every operand once (lower bound on traffic)
                      "compulsory_bytes_per_iteration": nnz * 8 + (n + 1) * 8 + 2 * n * d * 4},
-        "checks": {"finite": finite, "max_abs_row_norm_minus_1": norm_err},
+        "checks": checks,
         "placement_tuning": placement,
     }
     res.update(extra)
     if sg is not None and isinstance(comm, comm_mod.RcclComm) and world > 1:
         comm.check()                                   # a device-side wait that ran out of its budget is an error, not a number
     return res, a, b, iterate, blocks, sg
+
+
+def dump_outputs(path, a, n, budget_bytes=48 << 20, seed=0):
+    """--dump-outputs: the iterate the last timed step wrote — what a caller of the propagate loop receives — as float32 in
+    <path>/iterate.npy.  An iterate larger than `budget_bytes` is written as a fixed, seeded sample of its rows (ascending); the
+    rows' indices go to <path>/iterate_rows.npy (float64, exact) either way, so two builds are compared row for row."""
+    os.makedirs(path, exist_ok=True)
+    rows = max(1, budget_bytes // (a.shape[1] * 4))
+    idx = np.arange(n) if n <= rows else np.sort(np.random.default_rng(seed).choice(n, rows, replace=False))
+    sample = a[torch.from_numpy(idx).to(a.device)].cpu().numpy()
+    np.save(os.path.join(path, "iterate.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    np.save(os.path.join(path, "iterate_rows.npy"), idx.astype(np.float64))
 
 
 def finite_and_row_sumsq(a, n, rows_per_pass=4_000_000):
@@ -1108,6 +1132,24 @@ def run_whitened(args, g, x, dev, L, iters, hashes):
     return out
 
 
+def drift_at_scale_record():
+    """--full: end-to-end figures of the GPU suite at config 2's size (tests/test_gpu_parity_at_scale.py), quoted from the committed
+    record; a missing file or key is an error in the line, not an empty object (round 4 shipped one)."""
+    try:
+        pj = json.load(open(os.path.join(ROOT, "profiles", "r06_parity_at_scale.json")))
+        plain, dl = pj["plain_loop_c2"], pj["default_loop_40_iterations_c2"]
+        return {
+            "source": "profiles/r06_parity_at_scale.json (tests/test_gpu_parity_at_scale.py at BASELINE config 2's size; NOT measured in this run — "
+                      "this run's own multi-iteration checks are rows_bit_equal_after_those_iterations and plain_loop_vs_oracle_record)",
+            "plain_loop_bit_equal_to_oracle_through_iteration": plain["bit_equal_through_iteration"],
+            "plain_loop_with_CLEORA_F_HUB_SEGMENTS_max_abs_diff_after_10": plain["hub_segments_flag_max_abs_diff_after_10"],
+            "default_loop_max_abs_cosine_diff_vs_reference_order": {k: v["max_abs_cosine_diff_2000_rows"] for k, v in dl["vs_reference_order_on_gpu"].items()},
+            "default_loop_max_abs_cosine_diff_vs_oracle_loop": {"iterations": dl["vs_oracle_loop"]["iterations"], "value": dl["vs_oracle_loop"]["max_abs_cosine_diff_2000_rows"]},
+            "default_loop_stated_tolerance": 1e-4}
+    except Exception as ex:                               # noqa: BLE001
+        return {"error": f"profiles/r06_parity_at_scale.json missing or incomplete: {type(ex).__name__}: {ex}"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1129,14 +1171,22 @@ def main():
     ap.add_argument("--partition", default="both", choices=["both", "row", "column"],
                     help="multi-GPU partition(s) to measure: 'row' = row blocks + in-place all-gather of X (north_star's "
                          "layout); 'column' = each rank owns d/N columns of X (one all-reduce of n floats per "
-                         "iteration); both (default) measures the two: `value` is the row partition's, the column partition is reported in `partitions`")
+                         "iteration); both (default) measures the two with --full (`value` is the row partition's, the column partition is "
+                         "reported in `partitions`) and the row partition alone without it")
     ap.add_argument("--balance", default="auto", choices=["auto", "rows", "nnz"],
                     help="row partition: equal row counts, or balanced on the rowptr prefix sum")
     ap.add_argument("--no-placement", action="store_true",
                     help="plain allocations for the iterates instead of cleora_alloc_iterates (DESIGN.md §2.1)")
-    ap.add_argument("--whiten-iters", type=int, default=8, help="iterations of the whitened default loop (N = 1); 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the wall clock of the drop-in calls (embed_fast / embed, 40 iterations, host in / host out)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the oracle checks and the CPU baseline, the whitened default loop with its per-kernel figures, "
+                         "the end-to-end wall clock of the drop-in calls and, for N > 1, the partitions' self-test, the column partition and "
+                         "the sharded whitened loop.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the iterate the last of them computed (a fixed, seeded sample of its rows when it "
+                         "is large) to DIR/iterate.npy and the rows' indices to DIR/iterate_rows.npy")
+    ap.add_argument("--whiten-iters", type=int, default=8, help="--full: iterations of the whitened default loop; 0 = skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle checks and the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the wall clock of the drop-in calls (embed_fast / embed, 40 iterations, host in / host out)")
     ap.add_argument("--watchdog", type=int, default=1500, help="seconds before every thread's traceback is dumped and the run exits")
     ap.add_argument("--backend", default="rccl", choices=["rccl", "local", "gloo"],
                     help="N > 1: transport of the C-ABI communicator — rccl (RCCL over xGMI, csrc/comm.hip; the peer-direct all-gather is timed "
@@ -1146,6 +1196,12 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only: everything the switches below select belongs to --full
+        args.no_selftest = args.no_cpu_baseline = args.no_end_to_end = True
+        args.whiten_iters = 0
+        if args.partition == "both":
+            args.partition = "row"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started the way the driver starts the one-GPU run (`python bench.py --gpus N ...`, no torchrun): launch the ranks here
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -1210,6 +1266,8 @@ def main():
         if d % (4 * world) != 0 and "column" in parts:
             parts.remove("column")
             parts = parts or ["row"]
+    # `value` is north_star's layout — row partition + all-gather of X — whenever it is measured
+    args.headline = "row" if "row" in parts else parts[0]
 
     results, keep, whitened_sharded, cpu = {}, None, None, None
     for part in parts:
@@ -1328,26 +1386,12 @@ def main():
         if pt.get("untuned_launch_ms"):
             r["roofline"]["frac_untuned"] = r["roofline"]["algorithmic_bytes_per_launch"] / (pt["untuned_launch_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS
             r["roofline"]["frac_untuned_note"] = "median of three launches on the first allocation pair cleora_alloc_iterates drew (what a plain hipMalloc pair runs at)"
-        # end-to-end figures of the GPU suite at config 2's size (tests/test_gpu_parity_at_scale.py), quoted from the committed record;
-        # a missing file or key is an error in the line, not an empty object (round 4 shipped one)
-        ppath = os.path.join(ROOT, "profiles", "r06_parity_at_scale.json")
-        try:
-            pj = json.load(open(ppath))
-            plain, dl = pj["plain_loop_c2"], pj["default_loop_40_iterations_c2"]
-            r["checks"]["drift_at_scale"] = {
-                "source": "profiles/r06_parity_at_scale.json (tests/test_gpu_parity_at_scale.py at BASELINE config 2's size; NOT measured in this run — "
-                          "this run's own multi-iteration checks are rows_bit_equal_after_those_iterations and plain_loop_vs_oracle_record)",
-                "plain_loop_bit_equal_to_oracle_through_iteration": plain["bit_equal_through_iteration"],
-                "plain_loop_with_CLEORA_F_HUB_SEGMENTS_max_abs_diff_after_10": plain["hub_segments_flag_max_abs_diff_after_10"],
-                "default_loop_max_abs_cosine_diff_vs_reference_order": {k: v["max_abs_cosine_diff_2000_rows"] for k, v in dl["vs_reference_order_on_gpu"].items()},
-                "default_loop_max_abs_cosine_diff_vs_oracle_loop": {"iterations": dl["vs_oracle_loop"]["iterations"], "value": dl["vs_oracle_loop"]["max_abs_cosine_diff_2000_rows"]},
-                "default_loop_stated_tolerance": 1e-4}
-        except Exception as ex:                               # noqa: BLE001
-            r["checks"]["drift_at_scale"] = {"error": f"profiles/r06_parity_at_scale.json missing or incomplete: {type(ex).__name__}: {ex}"}
+        if args.full:
+            r["checks"]["drift_at_scale"] = drift_at_scale_record()
         out = {
             "metric": METRIC if args.config == "C3" else f"propagate iterations/sec & edges·dim/sec, BASELINE config {args.config}", "value": r["value"], "unit": "edge*dim/s",
             "iterations_per_sec": r["iterations_per_sec"],
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"], "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{workload_label}: n={n}, nnz={nnz}, d={d}, left Markov; one step = SpMM + fused L2 norm"

@@ -33,7 +33,7 @@ timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c2_sta
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/c2_fetch" -o pmc -- python "$root/scripts/pmc_probe.py" --graph c2 > "$out/c2_fetch.log" 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/c2_write" -o pmc -- python "$root/scripts/pmc_probe.py" --graph c2 > "$out/c2_write.log" 2>&1
 fi
-timeout 600 python "$root/bench.py" > "$out/bench_plain.log" 2>&1
+timeout 600 python "$root/bench.py" --full > "$out/bench_plain.log" 2>&1
 tail -1 "$out/bench_plain.log"
 for f in fetch write ea hit wpmc wlds winst c2_stats c2_fetch c2_write; do tail -1 "$out/$f.log" | cut -c1-200; done
 # keep the merge under the gpurun_out size limit: only the summaries that summarize_profile.py reads

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_sharing_the_gpu_without_torchrun():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--nodes", "300000", "--pairs", "2850000",
-                        "--steps", "3", "--warmup", "1", "--whiten-iters", "3"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--steps", "3", "--warmup", "1", "--whiten-iters", "3", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -47,7 +47,7 @@ def test_bench_eight_ranks_sharing_the_gpu_the_drivers_scale_invocation():
     self-test on three of eight ranks (a zero fill racing the peers' pushes) — a race two and three ranks never showed."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--nodes", "400000", "--pairs", "3800000",
-                        "--steps", "2", "--warmup", "1", "--whiten-iters", "2", "--partition", "row"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--steps", "2", "--warmup", "1", "--whiten-iters", "2", "--partition", "row", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout[-2000:]

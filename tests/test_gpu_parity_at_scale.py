@@ -144,7 +144,7 @@ def test_whitened_loop_at_c2_size_against_the_oracle_loop(c2, oracle_whitened):
 def test_whitened_loop_record_at_c2_size_is_what_the_live_oracle_computes_and_the_gpu_matches_it(c2, oracle_whitened):
     """the default loop at BASELINE's FULL sizes (config 3: 10M x 256, config 5: 2M x 1024) is pinned by
     records of the oracle's loop (tests/golden/whitened_loop_{C3,C5}.npz, written by tests/golden/make_whitened_loop_record.py on the
-    GPU box; bench.py compares the GPU with them in every run: `whitened.checks.vs_oracle_record`).  Here the same machinery at
+    GPU box; bench.py --full compares the GPU with them in every run: `whitened.checks.vs_oracle_record`).  Here the same machinery at
     config 2's size, where the oracle also runs LIVE: (1) the record equals what the live oracle loop computes (invariants to 1e-5:
     the oracle itself is only reproducible to the order of its BLAS's summation), (2) the GPU's default loop and its
     reference-order loop match the record within the stated tolerances — cosines and row norms 1e-4, spectrum 1e-4 of the largest
