@@ -9,7 +9,7 @@
 __version__ = "0.1.0"
 
 
-def install(devices=None, hub_segments=None):
+def install(devices=None, hub_segments=None, iterate_dtype=None):
     """Make this package's SparseMatrix the reference's compiled module: after this call
     `import pycleora` (the reference's unmodified Python package) binds
     `from .pycleora import SparseMatrix` (pycleora/__init__.py:4) to cleora_amd.pycleora.
@@ -19,11 +19,20 @@ def install(devices=None, hub_segments=None):
     CLEORA_DEVICES / CLEORA_DEVICE say (default: device 0).
     hub_segments: True = the loops sum rows of more than 256 edges in segments (CLEORA_F_HUB_SEGMENTS: not the reference's bits,
     within 2e-6 of the sum of |terms|) — the way out for a graph whose longest row is an in-order chain of 10^7 additions; None keeps
-    what CLEORA_HUB_SEGMENTS says (default: the reference's order)."""
+    what CLEORA_HUB_SEGMENTS says (default: the reference's order).
+    iterate_dtype: "f16" = embed_fast / embed_fast_convergence on one GPU keep their iterates in f16 between iterations
+    (CLEORA_F_ITERATE_F16: half the SpMM's gathered bytes, f32 arithmetic, NOT the reference's bits; rows longer than 256 edges take
+    the segmented sum); "f32" restores the default; None keeps the current setting.  Not combinable with `devices`."""
     import importlib.util
     import sys
 
     from . import pycleora as _mod
+    if iterate_dtype is not None:
+        if iterate_dtype not in ("f16", "f32"):
+            raise ValueError(f"iterate_dtype must be 'f16' or 'f32', got {iterate_dtype!r}")
+        if devices is not None:
+            raise ValueError("iterate_dtype is served on one GPU only: do not combine it with devices=[...]")
+        _mod.set_iterate_dtype(iterate_dtype)
     if devices is not None:
         _mod.set_devices(devices)
     if hub_segments is not None:

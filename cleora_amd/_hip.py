@@ -16,6 +16,7 @@ OK, E_INVALID, E_OOM, E_HIP, E_NODEVICE, E_RCCL = 0, -1, -2, -3, -4, -5
 LEFT, SYMMETRIC = 0, 1
 F_L2NORM, F_FASTNORM, F_RESIDUAL, F_SQDIFF, F_ROWSQ, F_SCALE, F_WHITEN = 1, 2, 4, 8, 16, 32, 64
 F_L1NORM, F_BLEND_ANY, F_SQDIFF64, F_HUB_SEGMENTS, F_ROWSQ_CONT = 128, 256, 512, 1024, 2048
+F_ITERATE_F16 = 4096
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 ALLGATHER_RING, ALLGATHER_P2P, ALLGATHER_PEER = 0, 1, 2
@@ -128,6 +129,9 @@ SIGNATURES = {
     "cleora_propagate_vals_dev": (c_int, [vp, vp, vp, c_u64, c_u32, vp, c_u64, c_u32, c_f32, vp, vp, vp, vp]),
     "cleora_propagate_attention_dev": (c_int, [vp, c_int, vp, c_u64, c_u32, c_f32, vp, c_u64, c_u32, c_f32, vp, vp, vp]),
     "cleora_edge_attention_dev": (c_int, [vp, c_int, vp, c_u64, c_u32, c_f32, vp, vp]),
+    "cleora_propagate_h_dev": (c_int, [vp, c_int, vp, c_u64, c_u32, vp, c_u64, c_u32, c_f32, vp, vp, vp]),
+    "cleora_convert_f32_to_f16_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u64, vp]),
+    "cleora_convert_f16_to_f32_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u64, vp]),
     "cleora_rowops_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u64, c_u32, c_f32, vp, vp, vp, vp]),
     "cleora_init_dev": (c_int, [vp, c_u64, c_u32, c_i64, vp, c_u64, vp]),
     "cleora_reduce_workspace": (c_u64, [c_u64]),
@@ -299,6 +303,17 @@ class Graph:
     def set_hot_cache(self, hot_bytes):
         """-1 automatic, 0 off, > 0 forced byte budget (include/cleora_hip.h)."""
         check(lib().cleora_graph_set_hot_cache(self.handle, int(hot_bytes)))
+
+    def propagate_h(self, kind, x, y, flags=0, residual_weight=0.0, x_self=None, row_sqdiff=None, stream=None):
+        """cleora_propagate_h_dev on float16 DevArrays: x (n_cols, d) -> y (n_rows, d), dense rows (ld = d); x_self / row_sqdiff
+        (float64 DevArray) as the flags need them.  Enqueues only."""
+        for a in (x, y, x_self):
+            if a is not None and a.dtype != np.float16:
+                raise ValueError("propagate_h takes float16 DevArrays")
+        d = x.shape[1]
+        check(lib().cleora_propagate_h_dev(self.handle, kind, x.ptr, d, d, y.ptr, d, int(flags), float(residual_weight),
+                                           x_self.ptr if x_self is not None else None,
+                                           row_sqdiff.ptr if row_sqdiff is not None else None, stream))
 
     def set_hub_inorder_min(self, min_edges):
         """Long rows with more than min_edges edges run on the in-order hub launch, the others first in the main launch (same bits)."""

@@ -211,6 +211,7 @@ void free_graph(cleora_graph *g) {
     (void)hipFree(g->seg_begin);
     (void)hipFree(g->hub_partial);
     (void)hipFree(g->col_hot);
+    (void)hipFree(g->col_hot_h);
     (void)hipFree(g->hot_meta);
     (void)hipFree(g->io_buf[0]);
     (void)hipFree(g->io_buf[1]);
@@ -396,7 +397,7 @@ int cleora_graph_get_info(const cleora_graph *g, cleora_graph_info *info) {
     info->n_hub_segments = g->n_hub_segments;
     {
         std::lock_guard<std::mutex> lock(g->mu);
-        info->device_bytes = g->device_bytes + (g->col_hot ? g->nnz * sizeof(uint32_t) : 0);
+        info->device_bytes = g->device_bytes + ((g->col_hot ? 1 : 0) + (g->col_hot_h ? 1 : 0)) * g->nnz * sizeof(uint32_t);
         info->hot_rows = hot_rows_marked(g);
     }
     info->hub_threshold = g->hub_threshold;
@@ -438,9 +439,11 @@ int cleora_graph_set_hot_cache(cleora_graph *g, int64_t hot_bytes) {
     g->hot_bytes = hot_bytes;
     g->hot_failed = false;
     g->hot_rows_target = 0;   // rebuild (or drop) the marks on the next launch
-    if (hot_bytes == 0 && g->col_hot) {
+    g->hot_rows_target_h = 0;
+    if (hot_bytes == 0) {
         (void)hipFree(g->col_hot);
-        g->col_hot = nullptr;
+        (void)hipFree(g->col_hot_h);
+        g->col_hot = g->col_hot_h = nullptr;
     }
     return CLEORA_OK;
 }
@@ -476,6 +479,20 @@ int cleora_propagate_dev(const cleora_graph *g, int markov_type, const float *x,
                          float *row_sumsq, void *stream) {
     return launch_propagate(g, markov_type, x, ldx, d, y, ldy, flags, residual_weight, x_self,
                             row_sqdiff, row_sumsq, S(stream));
+}
+
+int cleora_propagate_h_dev(const cleora_graph *g, int markov_type, const uint16_t *x_h, uint64_t ldx, uint32_t d, uint16_t *y_h,
+                           uint64_t ldy, uint32_t flags, float residual_weight, const uint16_t *x_self_h, double *row_sqdiff,
+                           void *stream) {
+    return launch_propagate_h(g, markov_type, x_h, ldx, d, y_h, ldy, flags, residual_weight, x_self_h, row_sqdiff, S(stream));
+}
+
+int cleora_convert_f32_to_f16_dev(const float *src, uint64_t ld_src, uint64_t n, uint32_t d, uint16_t *dst, uint64_t ld_dst, void *stream) {
+    return launch_convert_f32_to_f16(src, ld_src, n, d, dst, ld_dst, S(stream));
+}
+
+int cleora_convert_f16_to_f32_dev(const uint16_t *src, uint64_t ld_src, uint64_t n, uint32_t d, float *dst, uint64_t ld_dst, void *stream) {
+    return launch_convert_f16_to_f32(src, ld_src, n, d, dst, ld_dst, S(stream));
 }
 
 int cleora_propagate_vals_dev(const cleora_graph *g, const float *edge_vals_dev, const float *x, uint64_t ldx,
@@ -1125,6 +1142,9 @@ static int embed_impl(const cleora_graph *g, const uint64_t *entity_hash_host, c
     CL_REQUIRE(out_host != nullptr || x_dev != nullptr, "out is NULL");
     CL_REQUIRE(entity_hash_host != nullptr || x0_host != nullptr || x_dev != nullptr, "need entity hashes or x0");
     CL_REQUIRE(d > 0, "d must be positive");
+    const bool f16 = (flags & CLEORA_F_ITERATE_F16) != 0;
+    CL_REQUIRE(!(f16 && (flags & CLEORA_F_WHITEN)), "ITERATE_F16 is for the plain loop: the whitening kernels read f32 iterates");
+    CL_REQUIRE(!f16 || (d % 4 == 0 && d <= 2048), "ITERATE_F16: d must be a multiple of 4, at most 2048");
     CL_HIP(hipSetDevice(g->device));
     auto emit = [&](const float *result, uint64_t nbytes) -> int {
         if (x_dev) {
@@ -1147,8 +1167,8 @@ static int embed_impl(const cleora_graph *g, const uint64_t *entity_hash_host, c
         b.p = bufs[0];
         a.p = bufs[1];
         c.p = bufs[2];
-    } else if ((rc = a.alloc(bytes)) != CLEORA_OK || (rc = b.alloc(bytes)) != CLEORA_OK) {
-        return rc;
+    } else if ((rc = a.alloc(bytes)) != CLEORA_OK || (rc = b.alloc(f16 ? bytes / 2 : bytes)) != CLEORA_OK) {
+        return rc;                                       // (f16 iterates: `a` holds E_0 and later the widened result, `b` one f16 iterate)
     }
     // nobody looks at the intermediate whitened iterates when there is no convergence test: SpMM(t+1) beside Gram /
     // eigh(t) (embed_whitened_overlapped).  That loop wants E_0 in the SpMM-side buffer bufs[0] = `b`.
@@ -1181,6 +1201,39 @@ static int embed_impl(const cleora_graph *g, const uint64_t *entity_hash_host, c
             (rc = ws.alloc(reduce_workspace(n) * sizeof(double))) != CLEORA_OK ||
             (rc = total.alloc(sizeof(double))) != CLEORA_OK)
             return rc;
+    }
+    if (f16) {
+        // the plain loop on f16-stored iterates (spmm_h.hip): E_0 converted once, two f16 buffers ping-pong, the result widened
+        // back into `a`.  No placement search for the f16 buffers.
+        if ((rc = c.alloc(bytes / 2)) != CLEORA_OK) return rc;
+        uint16_t *src = b.as<uint16_t>(), *dst = c.as<uint16_t>();
+        if ((rc = launch_convert_f32_to_f16(a.as<float>(), d, n, d, src, d, nullptr)) != CLEORA_OK) return rc;
+        uint64_t actual = max_iterations;
+        const uint32_t base = CLEORA_F_L2NORM | CLEORA_F_RESIDUAL | (flags & CLEORA_F_FASTNORM);
+        CL_HIP(hipDeviceSynchronize());
+        const auto t_loop = std::chrono::steady_clock::now();
+        for (uint64_t it = 0; it < max_iterations; ++it) {
+            const bool test = check && it > 0;  // embedding.rs:169
+            rc = launch_propagate_h(g, markov_type, src, d, d, dst, d, base | (test ? CLEORA_F_SQDIFF : 0u), residual_weight, src,
+                                    test ? sq.as<double>() : nullptr, nullptr);
+            if (rc != CLEORA_OK) return rc;
+            std::swap(src, dst);
+            if (test) {
+                if ((rc = launch_reduce_sum(sq.as<double>(), n, ws.as<double>(), total.as<double>(), nullptr)) != CLEORA_OK) return rc;
+                double sum = 0.0;
+                CL_HIP(hipMemcpy(&sum, total.p, sizeof(double), hipMemcpyDeviceToHost));
+                const float rmse = sqrtf((float)(sum / (double)(n * (uint64_t)d)));      // embedding.rs:177-178
+                if (rmse < convergence_threshold) {
+                    actual = it + 1;
+                    break;
+                }
+            }
+        }
+        if ((rc = launch_convert_f16_to_f32(src, d, n, d, a.as<float>(), d, nullptr)) != CLEORA_OK) return rc;
+        CL_HIP(hipDeviceSynchronize());
+        g_last_loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count();
+        if (iterations_run) *iterations_run = actual;
+        return emit(a.as<float>(), bytes);
     }
     // Placement tuning on the job's own iterations (large iterates only): the SpMM runs up to 12 %
     // slower when the two ping-pong allocations fall into the same placement class.

@@ -94,6 +94,8 @@ struct cleora_graph {
     mutable uint32_t *col_hot = nullptr;
     mutable uint64_t hot_rows_target = 0;
     mutable uint32_t *hot_meta = nullptr;   // device: {threshold in-degree, rows marked}
+    mutable uint32_t *col_hot_h = nullptr;  // the marks for f16-stored rows (spmm_h.hip): twice the rows fit the same byte budget
+    mutable uint64_t hot_rows_target_h = 0;
     mutable bool hot_failed = false;        // building the marks failed once (e.g. out of memory): policy stays off
     mutable uint32_t auto_launches = 0;     // automatic mode arms itself on the third eligible launch
 
@@ -121,12 +123,19 @@ int launch_propagate(const cleora_graph *g, int kind, const float *x, uint64_t l
 int launch_rowops(const float *x, uint64_t ldx, uint64_t n, uint32_t d, float *y, uint64_t ldy,
                   uint32_t flags, float rw, const float *x_self, double *row_sqdiff,
                   float *row_sumsq, hipStream_t stream, uint64_t ldxs = 0);  // ldxs: leading dimension of x_self (0 = ldx)
+int ensure_hub_partial(const cleora_graph *g, uint32_t d, bool segmented, hipStream_t stream);   // the hub rows' f32 scratch (g->mu held)
+// spmm_h.hip: the same SpMM on f16-stored x / x_self / y (f32 in between; long rows always segmented)
+int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, uint16_t *y, uint64_t ldy,
+                       uint32_t flags, float rw, const uint16_t *x_self, double *row_sqdiff, hipStream_t stream);
 // hot.hip
-const uint32_t *ensure_hot_cols(const cleora_graph *g, uint32_t d, uint64_t ldx, hipStream_t stream);
+const uint32_t *ensure_hot_cols(const cleora_graph *g, uint32_t d, uint64_t ldx, hipStream_t stream,
+                                uint32_t elem_size = sizeof(float));   // bytes per stored element: the hot set is sized by row bytes
 uint64_t hot_rows_marked(const cleora_graph *g);
 // rowops.hip
 int launch_init(const uint64_t *hash, uint64_t n, uint32_t d, int64_t seed, float *x, uint64_t ldx,
                 hipStream_t stream);
+int launch_convert_f32_to_f16(const float *src, uint64_t lds, uint64_t n, uint32_t d, uint16_t *dst, uint64_t ldd, hipStream_t stream);
+int launch_convert_f16_to_f32(const uint16_t *src, uint64_t lds, uint64_t n, uint32_t d, float *dst, uint64_t ldd, hipStream_t stream);
 uint64_t reduce_workspace(uint64_t n);
 int launch_reduce_sum(const double *v, uint64_t n, double *ws, double *out, hipStream_t stream);
 uint64_t colsum_workspace(uint64_t n, uint32_t d);

@@ -72,18 +72,21 @@ __global__ __launch_bounds__(256) void mark_kernel(const uint32_t *__restrict__ 
 }  // namespace
 
 namespace {
-const uint32_t *build_hot_cols(const cleora_graph *g, uint64_t want, hipStream_t stream);
+const uint32_t *build_hot_cols(const cleora_graph *g, uint64_t want, hipStream_t stream, uint32_t *&col_hot, uint64_t &target);
 }
 
-// Returns the marked column array for rows of `d` floats (building or rebuilding it if needed), or
+// Returns the marked column array for rows of `d` elements of elem_size bytes (building or rebuilding it if needed), or
 // nullptr when the policy does not apply.  Called with g->mu held.  Everything it does is ENQUEUED on `stream`
 // (stream-ordered allocations, kernels; the threshold is chosen on the device): a `*_dev` entry point never
-// synchronises, allocates with hipMalloc or copies to the host because of it.
+// synchronises, allocates with hipMalloc or copies to the host because of it.  f16-stored rows (elem_size 2) keep marks of their
+// own beside the f32 ones — the same byte budget holds twice the rows — so a handle that serves both never rebuilds per launch.
 
-const uint32_t *ensure_hot_cols(const cleora_graph *g, uint32_t d, uint64_t ldx, hipStream_t stream) {
+const uint32_t *ensure_hot_cols(const cleora_graph *g, uint32_t d, uint64_t ldx, hipStream_t stream, uint32_t elem_size) {
     if (g->hot_bytes == 0 || g->hot_failed || g->nnz == 0 || g->n_cols >= (1ull << 31)) return nullptr;
-    const uint64_t row_bytes = (uint64_t)d * sizeof(float);
-    const uint64_t x_bytes = g->n_cols * ldx * sizeof(float);
+    const uint64_t row_bytes = (uint64_t)d * elem_size;
+    const uint64_t x_bytes = g->n_cols * ldx * elem_size;
+    uint32_t *&col_hot = elem_size == sizeof(float) ? g->col_hot : g->col_hot_h;
+    uint64_t &target = elem_size == sizeof(float) ? g->hot_rows_target : g->hot_rows_target_h;
     uint64_t budget;
     if (g->hot_bytes < 0) {                           // auto: only when X is far larger than the caches ...
         if (x_bytes < (1ull << 30)) return nullptr;
@@ -101,8 +104,8 @@ const uint32_t *ensure_hot_cols(const cleora_graph *g, uint32_t d, uint64_t ldx,
     uint64_t want = budget / row_bytes;
     if (want > g->n_cols / 2) want = g->n_cols / 2;
     if (want == 0) return nullptr;
-    if (g->col_hot && g->hot_rows_target == want) return g->col_hot;
-    const uint32_t *marked = build_hot_cols(g, want, stream);
+    if (col_hot && target == want) return col_hot;
+    const uint32_t *marked = build_hot_cols(g, want, stream, col_hot, target);
     if (!marked) {
         // the policy is an optimisation: a failure here (typically out of memory for the marked copy) must not
         // fail the launch or be retried on every call — clear the sticky HIP error and switch the policy off
@@ -113,7 +116,7 @@ const uint32_t *ensure_hot_cols(const cleora_graph *g, uint32_t d, uint64_t ldx,
 }
 
 namespace {
-const uint32_t *build_hot_cols(const cleora_graph *g, uint64_t want, hipStream_t stream) {
+const uint32_t *build_hot_cols(const cleora_graph *g, uint64_t want, hipStream_t stream, uint32_t *&col_hot, uint64_t &target) {
     if (hipSetDevice(g->device) != hipSuccess) return nullptr;
     // a rebuild overwrites col_hot in place, ordered on `stream` like every launch of this handle (one stream per
     // handle: include/cleora_hip.h)
@@ -124,9 +127,9 @@ const uint32_t *build_hot_cols(const cleora_graph *g, uint64_t want, hipStream_t
         return nullptr;
     }
     if (!g->hot_meta && hipMallocAsync(reinterpret_cast<void **>(&g->hot_meta), 2 * sizeof(uint32_t), stream) != hipSuccess) g->hot_meta = nullptr;
-    if (g->hot_meta && !g->col_hot && hipMallocAsync(reinterpret_cast<void **>(&g->col_hot), g->nnz * sizeof(uint32_t), stream) != hipSuccess)
-        g->col_hot = nullptr;
-    if (!g->hot_meta || !g->col_hot) {
+    if (g->hot_meta && !col_hot && hipMallocAsync(reinterpret_cast<void **>(&col_hot), g->nnz * sizeof(uint32_t), stream) != hipSuccess)
+        col_hot = nullptr;
+    if (!g->hot_meta || !col_hot) {
         (void)hipFreeAsync(indeg, stream);
         (void)hipFreeAsync(bins, stream);
         return nullptr;
@@ -137,13 +140,13 @@ const uint32_t *build_hot_cols(const cleora_graph *g, uint64_t want, hipStream_t
     hipLaunchKernelGGL(indegree_kernel, grid, dim3(256), 0, stream, g->col, g->nnz, indeg);
     hipLaunchKernelGGL(degree_hist_kernel, grid, dim3(256), 0, stream, indeg, g->n_cols, bins);
     hipLaunchKernelGGL(select_threshold_kernel, dim3(1), dim3(64), 0, stream, bins, want, g->hot_meta);
-    hipLaunchKernelGGL(mark_kernel, grid, dim3(256), 0, stream, g->col, g->nnz, indeg, g->hot_meta, g->col_hot);
+    hipLaunchKernelGGL(mark_kernel, grid, dim3(256), 0, stream, g->col, g->nnz, indeg, g->hot_meta, col_hot);
     const bool ok = hipGetLastError() == hipSuccess;
     (void)hipFreeAsync(indeg, stream);
     (void)hipFreeAsync(bins, stream);
     if (!ok) return nullptr;
-    g->hot_rows_target = want;
-    return g->col_hot;
+    target = want;
+    return col_hot;
 }
 }  // namespace
 

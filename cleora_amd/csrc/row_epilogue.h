@@ -93,15 +93,12 @@ __device__ __forceinline__ void store_row(float *__restrict__ p, int gl, uint32_
     }
 }
 
-// Residual blend, L2 normalise, squared difference, store — on the accumulator registers.
-template <int G, int V, int W, bool FULL>
-__device__ __forceinline__ void finish_row(const RowArgs &ra, uint64_t row, int gl, int gbase,
-                                           float (&acc)[V][W]) {
+// Residual blend and L1 / L2 normalisation on the accumulator registers (xs: the row of x_self, read when RESIDUAL is set): the
+// arithmetic of finish_row, shared with the f16-stored rows of spmm_h.hip, which load and store differently around it.
+template <int G, int V, int W>
+__device__ __forceinline__ void blend_and_normalize(const RowArgs &ra, uint64_t row, int gl, int gbase,
+                                                    float (&acc)[V][W], const float (&xs)[V][W]) {
     const uint32_t d = ra.d;
-    float xs[V][W];
-    if (ra.flags & (CLEORA_F_RESIDUAL | CLEORA_F_SQDIFF))
-        load_row<G, V, W, FULL>(ra.x_self + row * ra.ldxs, gl, d, xs);
-
     if (ra.flags & CLEORA_F_RESIDUAL) {
         // dst[j] = alpha * dst[j] + rw * src[j]                      (src/embedding.rs:121-129)
 #pragma unroll
@@ -159,6 +156,18 @@ __device__ __forceinline__ void finish_row(const RowArgs &ra, uint64_t row, int 
                 for (int q = 0; q < W; ++q) acc[v][q] = fmul(acc[v][q], inv);
         }
     }
+}
+
+// Residual blend, L2 normalise, squared difference, store — on the accumulator registers.
+template <int G, int V, int W, bool FULL>
+__device__ __forceinline__ void finish_row(const RowArgs &ra, uint64_t row, int gl, int gbase,
+                                           float (&acc)[V][W]) {
+    const uint32_t d = ra.d;
+    float xs[V][W];
+    if (ra.flags & (CLEORA_F_RESIDUAL | CLEORA_F_SQDIFF))
+        load_row<G, V, W, FULL>(ra.x_self + row * ra.ldxs, gl, d, xs);
+
+    blend_and_normalize<G, V, W>(ra, row, gl, gbase, acc, xs);
 
     if (ra.flags & CLEORA_F_SQDIFF) {
         // delta = dst - src (f32, as the reference), accumulated in f64 instead of the

@@ -195,7 +195,51 @@ __global__ __launch_bounds__(256) void csr_rowsum_kernel(const uint64_t *__restr
     }
 }
 
+// ---- f32 <-> f16 storage conversion (the iterates of spmm_h.hip) ------------------------------------
+// Streaming, one pass: a thread converts W consecutive elements of one row.  f32 -> f16 rounds to nearest even and keeps
+// subnormals (v_cvt_f16_f32); f16 -> f32 is exact.
+template <int W, class Src, class Dst>
+__global__ __launch_bounds__(256) void convert_kernel(const Src *__restrict__ src, uint64_t lds, uint64_t n, uint32_t d,
+                                                      Dst *__restrict__ dst, uint64_t ldd) {
+    const uint32_t per_row = d / W;
+    const uint64_t i = CLEORA_LINEAR_BLOCK() * 256 + threadIdx.x;
+    const uint64_t row = i / per_row;
+    if (row >= n) return;
+    const uint32_t j = (uint32_t)(i - row * per_row) * W;
+    if constexpr (W == 1) {
+        dst[row * ldd + j] = (Dst)src[row * lds + j];
+    } else {
+        typedef Src src_v __attribute__((ext_vector_type(W)));
+        typedef Dst dst_v __attribute__((ext_vector_type(W)));
+        *reinterpret_cast<dst_v *>(dst + row * ldd + j) = __builtin_convertvector(*reinterpret_cast<const src_v *>(src + row * lds + j), dst_v);
+    }
+}
+
+template <class Src, class Dst>
+int launch_convert(const Src *src, uint64_t lds, uint64_t n, uint32_t d, Dst *dst, uint64_t ldd, hipStream_t stream) {
+    CL_REQUIRE(d > 0 && lds >= d && ldd >= d, "bad d / leading dimension");
+    CL_REQUIRE(src != nullptr && dst != nullptr, "src / dst is NULL");
+    if (n == 0) return CLEORA_OK;
+    // four elements per thread where both sides allow the vector access (16 bytes of f32, 8 of f16)
+    const bool w4 = d % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & (4 * sizeof(Src) - 1)) == 0 &&
+                    (reinterpret_cast<uintptr_t>(dst) & (4 * sizeof(Dst) - 1)) == 0;
+    const uint64_t threads = n * (uint64_t)(w4 ? d / 4 : d);
+    const dim3 grid = grid_1d_as_2d((threads + 255) / 256);
+    if (w4) hipLaunchKernelGGL((convert_kernel<4, Src, Dst>), grid, dim3(256), 0, stream, src, lds, n, d, dst, ldd);
+    else hipLaunchKernelGGL((convert_kernel<1, Src, Dst>), grid, dim3(256), 0, stream, src, lds, n, d, dst, ldd);
+    CL_HIP(hipGetLastError());
+    return CLEORA_OK;
+}
+
 }  // namespace
+
+int launch_convert_f32_to_f16(const float *src, uint64_t lds, uint64_t n, uint32_t d, uint16_t *dst, uint64_t ldd, hipStream_t stream) {
+    return launch_convert(src, lds, n, d, reinterpret_cast<_Float16 *>(dst), ldd, stream);
+}
+
+int launch_convert_f16_to_f32(const uint16_t *src, uint64_t lds, uint64_t n, uint32_t d, float *dst, uint64_t ldd, hipStream_t stream) {
+    return launch_convert(reinterpret_cast<const _Float16 *>(src), lds, n, d, dst, ldd, stream);
+}
 
 int launch_csr_rowsum(const cleora_graph *g, int kind, float *out, hipStream_t stream, float *abs_out) {
     CL_REQUIRE(g != nullptr && out != nullptr, "graph / out is NULL");

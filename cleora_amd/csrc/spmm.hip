@@ -913,6 +913,8 @@ int propagate_panel(const cleora_graph *g, SpmmArgs a, bool w4, bool segmented, 
 
 }  // namespace
 
+int ensure_hub_partial(const cleora_graph *g, uint32_t d, bool segmented, hipStream_t stream) { return ensure_partial(g, d, segmented, stream); }
+
 int launch_propagate(const cleora_graph *g, int kind, const float *x, uint64_t ldx, uint32_t d,
                      float *y, uint64_t ldy, uint32_t flags, float rw, const float *x_self,
                      double *row_sqdiff, float *row_sumsq, hipStream_t stream, const float *val_override, hipEvent_t *hub_join_out) {

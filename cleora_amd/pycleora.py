@@ -50,6 +50,19 @@ def set_hub_segments(on):
     _HUB_SEGMENTS = None if on is None else bool(on)
 
 
+_ITERATE_F16 = False    # set by cleora_amd.install(iterate_dtype=...)
+
+
+def set_iterate_dtype(dtype):
+    """How embed_fast / embed_fast_convergence store their iterates between iterations on the one-GPU path: "f32" (default, the
+    reference's bits) or "f16" (CLEORA_F_ITERATE_F16: half the gathered bytes, f32 arithmetic, one rounding per element and
+    iteration; not the reference's bits).  pycleora.embed() with whitening does not look at it."""
+    global _ITERATE_F16
+    if dtype not in ("f16", "f32"):
+        raise ValueError(f"iterate_dtype must be 'f16' or 'f32', got {dtype!r}")
+    _ITERATE_F16 = dtype == "f16"
+
+
 def loop_flags():
     on = _HUB_SEGMENTS if _HUB_SEGMENTS is not None else os.environ.get("CLEORA_HUB_SEGMENTS", "").strip() not in ("", "0")
     return _hip.F_HUB_SEGMENTS if on else 0
@@ -191,13 +204,15 @@ class SparseMatrix:
         ran = ctypes.c_uint64(0)
         with self._lock:
             m = self._multi()
+            if m is not None and _ITERATE_F16:
+                raise ValueError("iterate_dtype='f16' is served on one GPU only")
             if m is not None:
                 return m.embed(self._arr["hashes"], None, _PROPAGATIONS[propagation], d, iterations, seed, residual_weight, threshold, loop_flags())
             g = self._graph()
             _hip.check(_hip.lib().cleora_embed(
                 g.handle, _hip.ptr(self._arr["hashes"]), None, _PROPAGATIONS[propagation], d,
-                int(iterations), int(seed), float(residual_weight), float(threshold), loop_flags(),
-                _hip.ptr(out), ctypes.byref(ran)))
+                int(iterations), int(seed), float(residual_weight), float(threshold),
+                loop_flags() | (_hip.F_ITERATE_F16 if _ITERATE_F16 else 0), _hip.ptr(out), ctypes.byref(ran)))
         return out, int(ran.value)
 
     def embed_fast(self, feature_dim, num_iterations, propagation="left", seed=0,

@@ -75,6 +75,8 @@ extern "C" {
                                    * out: that sum extended over this call's d columns, the reference's order src/embedding.rs:94-97) — the
                                    * column partition hands a row's running sum from rank to rank so that the L2 norm is the one-GPU sum bit
                                    * for bit (csrc/colsharded.hip) */
+#define CLEORA_F_ITERATE_F16 4096u /* cleora_embed / cleora_embed_dev, plain loop only: the iterates are STORED as IEEE binary16 between
+                                    * iterations (cleora_propagate_h_dev).  Opt-in and not the reference's bits; see cleora_embed */
 
 typedef struct cleora_graph cleora_graph; /* device-resident CSR shard (struct SparseMatrix, src/sparse_matrix.rs:56-78) */
 
@@ -202,6 +204,22 @@ int cleora_propagate_dev(const cleora_graph *g, int markov_type, const float *x,
                          uint32_t d, float *y, uint64_t ldy, uint32_t flags,
                          float residual_weight, const float *x_self, double *row_sqdiff,
                          float *row_sumsq, void *stream);
+
+/* The same SpMM on f16-STORED rows (csrc/spmm_h.hip): x_h, x_self_h and y_h hold IEEE binary16 bits, everything between the load
+ * and the store is f32.  A gathered element is widened exactly; the row sum is the same separate f32 multiply and add in stored edge
+ * order; the epilogue runs on the f32 sums; every element is then rounded ONCE (to nearest even, subnormals kept) to f16, and
+ * SQDIFF / SQDIFF64 are taken after that rounding, between the stored value and x_self (both widened).  Same flags as
+ * cleora_propagate_dev except: ROWSQ, SCALE and ROWSQ_CONT are CLEORA_E_INVALID, and HUB_SEGMENTS is implied (rows longer than
+ * hub_threshold are always summed in segments: within 2e-6 of the sum of |terms|, deterministic).  Serves d % 4 == 0, d <= 2048,
+ * ldx % 4 == 0, ldy % 4 == 0 and 8-byte-aligned pointers; anything else is CLEORA_E_INVALID (no scalar and no panel path).  The
+ * hot-row cache policy is sized by row bytes, so twice the rows of the f32 policy fit the budget. */
+int cleora_propagate_h_dev(const cleora_graph *g, int markov_type, const uint16_t *x_h, uint64_t ldx, uint32_t d, uint16_t *y_h,
+                           uint64_t ldy, uint32_t flags, float residual_weight, const uint16_t *x_self_h, double *row_sqdiff,
+                           void *stream);
+
+/* Storage conversion of an n x d matrix: f32 -> f16 rounds to nearest even and keeps subnormals, f16 -> f32 is exact. */
+int cleora_convert_f32_to_f16_dev(const float *src, uint64_t ld_src, uint64_t n, uint32_t d, uint16_t *dst, uint64_t ld_dst, void *stream);
+int cleora_convert_f16_to_f32_dev(const uint16_t *src, uint64_t ld_src, uint64_t n, uint32_t d, float *dst, uint64_t ld_dst, void *stream);
 
 /* The same SpMM with CALLER-SUPPLIED per-edge values (f32[nnz], the graph's edge order) in place of the stored
  * Markov values: the `weighted_adj @ embeddings` step of the reference's re-weighted variants
@@ -625,7 +643,13 @@ int cleora_whiten(const float *x_host, uint64_t n, uint32_t d, uint32_t n_compon
  * (potrf + trtri) instead of the eigensolver, falling back to it when the covariance is near-singular; the last iteration is
  * always the PCA form.  Results agree with the sequential order to f32 rounding (measured at |V| = 1M, d = 256: 5e-7 on pairwise
  * cosines after 10, 20 and 40 iterations).  The reference's order is what a convergence threshold selects (the tests pass one that is
- * never met); there are no environment switches. */
+ * never met); there are no environment switches.
+ * With CLEORA_F_ITERATE_F16 the PLAIN loop keeps its iterates in f16: the init (or x0) is f32 and converted once, the loop
+ * ping-pongs two f16 iterates through cleora_propagate_h_dev (L2, residual for 0 < rw < 1, the RMSE stop with f64 accumulation in
+ * fixed order — the RMSE of the f16 iterates the loop holds), and the result is widened into the f32 output (cleora_embed_dev keeps
+ * its f32 in / out buffer).  Rows need d % 4 == 0, d <= 2048.  Long rows take the segmented sum.  The placement search is skipped
+ * for the f16 buffers.  Together with CLEORA_F_WHITEN the flag is CLEORA_E_INVALID (the whitening kernels read f32), and so it is
+ * in cleora_embed_sharded, cleora_embed_colsharded and cleora_multi_embed. */
 int cleora_embed(const cleora_graph *g, const uint64_t *entity_hash_host, const float *x0_host,
                  int markov_type, uint32_t d, uint64_t max_iterations, int64_t seed,
                  float residual_weight, float convergence_threshold, uint32_t flags,
