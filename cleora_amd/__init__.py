@@ -9,7 +9,7 @@
 __version__ = "0.1.0"
 
 
-def install(devices=None, hub_segments=None, iterate_dtype=None):
+def install(devices=None, hub_segments=None, iterate_dtype=None, gather_dtype=None):
     """Make this package's SparseMatrix the reference's compiled module: after this call
     `import pycleora` (the reference's unmodified Python package) binds
     `from .pycleora import SparseMatrix` (pycleora/__init__.py:4) to cleora_amd.pycleora.
@@ -22,7 +22,11 @@ def install(devices=None, hub_segments=None, iterate_dtype=None):
     what CLEORA_HUB_SEGMENTS says (default: the reference's order).
     iterate_dtype: "f16" = embed_fast / embed_fast_convergence on one GPU keep their iterates in f16 between iterations
     (CLEORA_F_ITERATE_F16: half the SpMM's gathered bytes, f32 arithmetic, NOT the reference's bits; rows longer than 256 edges take
-    the segmented sum); "f32" restores the default; None keeps the current setting.  Not combinable with `devices`."""
+    the segmented sum); "f32" restores the default; None keeps the current setting.  Not combinable with `devices`.
+    gather_dtype: "f16" = the whitened one-call loop of cleora_amd.embed.embed() on one GPU gathers an f16 copy of its normalised rows
+    in every SpMM after the first (CLEORA_F_GATHER_F16: half the gathered bytes; sums, statistics and projections stay f32; NOT the
+    reference's bits).  A preference: calls with a convergence threshold or a callback run in f32 as before.  "f32" restores the
+    default; None keeps the current setting.  Not combinable with `devices`."""
     import importlib.util
     import sys
 
@@ -33,6 +37,12 @@ def install(devices=None, hub_segments=None, iterate_dtype=None):
         if devices is not None:
             raise ValueError("iterate_dtype is served on one GPU only: do not combine it with devices=[...]")
         _mod.set_iterate_dtype(iterate_dtype)
+    if gather_dtype is not None:
+        if gather_dtype not in ("f16", "f32"):
+            raise ValueError(f"gather_dtype must be 'f16' or 'f32', got {gather_dtype!r}")
+        if devices is not None:
+            raise ValueError("gather_dtype is served on one GPU only: do not combine it with devices=[...]")
+        _mod.set_gather_dtype(gather_dtype)
     if devices is not None:
         _mod.set_devices(devices)
     if hub_segments is not None:

@@ -17,6 +17,7 @@ LEFT, SYMMETRIC = 0, 1
 F_L2NORM, F_FASTNORM, F_RESIDUAL, F_SQDIFF, F_ROWSQ, F_SCALE, F_WHITEN = 1, 2, 4, 8, 16, 32, 64
 F_L1NORM, F_BLEND_ANY, F_SQDIFF64, F_HUB_SEGMENTS, F_ROWSQ_CONT = 128, 256, 512, 1024, 2048
 F_ITERATE_F16 = 4096
+F_GATHER_F16 = 8192
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 ALLGATHER_RING, ALLGATHER_P2P, ALLGATHER_PEER = 0, 1, 2
@@ -130,6 +131,7 @@ SIGNATURES = {
     "cleora_propagate_attention_dev": (c_int, [vp, c_int, vp, c_u64, c_u32, c_f32, vp, c_u64, c_u32, c_f32, vp, vp, vp]),
     "cleora_edge_attention_dev": (c_int, [vp, c_int, vp, c_u64, c_u32, c_f32, vp, vp]),
     "cleora_propagate_h_dev": (c_int, [vp, c_int, vp, c_u64, c_u32, vp, c_u64, c_u32, c_f32, vp, vp, vp]),
+    "cleora_propagate_hf_dev": (c_int, [vp, c_int, vp, c_u64, c_u32, vp, c_u64, c_u32, vp]),
     "cleora_convert_f32_to_f16_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u64, vp]),
     "cleora_convert_f16_to_f32_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u64, vp]),
     "cleora_rowops_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u64, c_u32, c_f32, vp, vp, vp, vp]),
@@ -147,6 +149,8 @@ SIGNATURES = {
     "cleora_csr_rowsums_dev": (c_int, [vp, c_int, vp, vp, vp]),
     "cleora_project_bounded_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, vp, c_u32, vp, c_u64, vp, vp, c_int, ctypes.POINTER(c_int),
                                            ctypes.POINTER(c_int), vp]),
+    "cleora_project_bounded_h_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, vp, c_u32, vp, c_u64, vp, vp, c_int, ctypes.POINTER(c_int),
+                                             ctypes.POINTER(c_int), vp, c_u64, vp]),
     "cleora_mean_dev": (c_int, [vp, c_u64, c_u32, vp, vp, vp]),
     "cleora_eigh_workspace": (c_u64, [c_u32]),
     "cleora_whiten_transform_dev": (c_int, [vp, c_u64, c_u32, c_u32, vp, vp, vp, vp]),
@@ -314,6 +318,14 @@ class Graph:
         check(lib().cleora_propagate_h_dev(self.handle, kind, x.ptr, d, d, y.ptr, d, int(flags), float(residual_weight),
                                            x_self.ptr if x_self is not None else None,
                                            row_sqdiff.ptr if row_sqdiff is not None else None, stream))
+
+    def propagate_hf(self, kind, x, y, flags=0, stream=None):
+        """cleora_propagate_hf_dev: x (n_cols, d) float16 -> y (n_rows, d) float32 DevArrays, dense rows (ld = d); flags: L2NORM /
+        L1NORM / FASTNORM.  Enqueues only."""
+        if x.dtype != np.float16 or y.dtype != np.float32:
+            raise ValueError("propagate_hf takes a float16 x and a float32 y")
+        d = x.shape[1]
+        check(lib().cleora_propagate_hf_dev(self.handle, kind, x.ptr, d, d, y.ptr, d, int(flags), stream))
 
     def set_hub_inorder_min(self, min_edges):
         """Long rows with more than min_edges edges run on the in-order hub launch, the others first in the main launch (same bits)."""

@@ -487,6 +487,11 @@ int cleora_propagate_h_dev(const cleora_graph *g, int markov_type, const uint16_
     return launch_propagate_h(g, markov_type, x_h, ldx, d, y_h, ldy, flags, residual_weight, x_self_h, row_sqdiff, S(stream));
 }
 
+int cleora_propagate_hf_dev(const cleora_graph *g, int markov_type, const uint16_t *x_h, uint64_t ldx, uint32_t d, float *y_f32,
+                            uint64_t ldy, uint32_t flags, void *stream) {
+    return launch_propagate_hf(g, markov_type, x_h, ldx, d, y_f32, ldy, flags, S(stream));
+}
+
 int cleora_convert_f32_to_f16_dev(const float *src, uint64_t ld_src, uint64_t n, uint32_t d, uint16_t *dst, uint64_t ld_dst, void *stream) {
     return launch_convert_f32_to_f16(src, ld_src, n, d, dst, ld_dst, S(stream));
 }
@@ -629,6 +634,22 @@ int cleora_project_bounded_dev(const float *x, uint64_t ldx, uint64_t n, uint32_
     if (norm_done) *norm_done = done ? 1 : 0;
     if (form && bounded) *form = 2;
     return rc;
+}
+
+int cleora_project_bounded_h_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *mean_f32_dev,
+                                 const float *transform_dev, uint32_t k, float *out, uint64_t ldo, const float *rowscale_dev,
+                                 const float *rowbound_dev, int norm, int *norm_done, int *form, uint16_t *out_h, uint64_t ldo_h,
+                                 void *stream) {
+    CL_REQUIRE(norm == 1 || norm == 2, "the f16 copy is a copy of normalised rows: norm must be 1 or 2");
+    CL_REQUIRE(d > 0 && k > 0 && ldx >= d && ldo >= k && ldo_h >= k, "bad d / k / leading dimension");
+    CL_REQUIRE(x != nullptr && mean_f32_dev != nullptr && transform_dev != nullptr && out != nullptr && out_h != nullptr,
+               "x / mean / transform / out / out_h is NULL");
+    CL_REQUIRE((const void *)x != (const void *)out, "x and out must not alias");
+    CL_REQUIRE(n > 0 && project_f16_applies(x, ldx, n, d, k, out, ldo, nullptr),
+               "the projection with an f16 copy is served where the f16 form applies: d = k = 256, 16-byte aligned rows");
+    if (form) *form = 1;
+    if (norm_done) *norm_done = 1;
+    return launch_project_f16(x, ldx, n, mean_f32_dev, transform_dev, out, ldo, S(stream), rowscale_dev, rowbound_dev, norm, out_h, ldo_h);
 }
 
 int cleora_csr_rowsum_dev(const cleora_graph *g, int markov_type, float *rowsum_dev, void *stream) {
@@ -947,8 +968,13 @@ namespace {
 // GEMM sees Z instead of A's input; tests carry the same tolerances as for the sequential loop).  Used when nobody
 // needs the intermediate whitened iterates (no convergence test here; the Python driver keeps callbacks sequential).
 //   b0 = the SpMM's destination in every launch (cleora_alloc_iterates' bufs[0]); b1 / b2 hold Y in turn.
+//   yh != nullptr (CLEORA_F_GATHER_F16): an n x d f16 copy of Y, rounded to nearest even.  Every SpMM from the second on gathers IT
+//   (launch_propagate_hf: f32 sums, f32 Z in b0) — Y's rows are normalised, |Y| <= 1; the first launch (A E_0, user data) stays f32.
+//   The copy comes out of the f16 projection's epilogue where that form runs (d = 256, no blend); every other producer of Y — Y_0,
+//   the split projection, the blend, the stand-alone norm pass, the n = 1 row pass — is followed by one convert pass.  Statistics,
+//   the d x d step and the final whitening read the f32 Y as before.
 int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float *b2, int markov_type, uint32_t d,
-                              uint64_t iterations, float rw, uint32_t flags, float **result) {
+                              uint64_t iterations, float rw, uint32_t flags, float **result, uint16_t *yh = nullptr) {
     const uint64_t n = g->n_rows;
     const uint32_t norm = (flags & CLEORA_F_L1NORM) ? CLEORA_F_L1NORM : CLEORA_F_L2NORM;
     const uint32_t fast = flags & (CLEORA_F_FASTNORM | CLEORA_F_HUB_SEGMENTS);
@@ -1005,6 +1031,7 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
     if ((rc = launch_propagate(g, markov_type, b0, d, d, b1, d, norm | fast | CLEORA_F_RESIDUAL | CLEORA_F_BLEND_ANY, rw, b0,
                                nullptr, nullptr, st.a)) != CLEORA_OK)
         return rc;
+    if (yh && iterations > 1 && (rc = launch_convert_f32_to_f16(b1, d, n, d, yh, d, st.a)) != CLEORA_OK) return rc;
     float *y = b1, *ynext = b2;
     const float *mean32, *transform;
     whiten_fit_result(ws.p, n, d, &mean32, &transform);
@@ -1020,7 +1047,10 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
             CL_HIP(hipEventRecord(st.gs, st.b));
             CL_HIP(hipStreamWaitEvent(st.a, st.gs, 0));
         }
-        if ((rc = launch_propagate(g, markov_type, y, d, d, b0, d, 0, 0.f, nullptr, nullptr, nullptr, st.a)) != CLEORA_OK) return rc;
+        rc = yh ? launch_propagate_hf(g, markov_type, yh, d, d, b0, d, 0, st.a)
+                : launch_propagate(g, markov_type, y, d, d, b0, d, 0, 0.f, nullptr, nullptr, nullptr, st.a);
+        if (rc != CLEORA_OK) return rc;
+        const bool copy = yh && it + 2 < iterations;       // the next SpMM gathers the Y this iteration makes (same stream: in order)
         // intermediate iterations of the L2-normalised loop may take ANY whitening transform (eigh.hip): Cholesky — unless the
         // guard refuses it on statistics that are only ~1e-8 accurate: then this iteration's statistics are taken again in f64
         // and the PCA form follows (rare: a near-singular covariance; e.g. d > rank)
@@ -1039,7 +1069,7 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
             bool normed = false;
             if (f16_project) {
                 rc = launch_project_f16(b0, d, n, mean32, transform, ynext, d, st.a, rowsum.as<float>(), rowabs.as<float>(),
-                                        norm == CLEORA_F_L1NORM ? 2 : 1);
+                                        norm == CLEORA_F_L1NORM ? 2 : 1, copy ? yh : nullptr, d);
                 normed = true;
             } else {
                 rc = launch_project(b0, d, n, d, mean32, transform, d, ynext, d, st.a, rowsum.as<float>(), blend ? y : nullptr, d,
@@ -1055,6 +1085,7 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
             if ((rc = launch_rowops(b0, d, n, d, ynext, d, norm | fast | CLEORA_F_RESIDUAL | CLEORA_F_BLEND_ANY, rw, y, nullptr, nullptr, st.a)) != CLEORA_OK)
                 return rc;
         }
+        if (copy && !(n > 1 && f16_project) && (rc = launch_convert_f32_to_f16(ynext, d, n, d, yh, d, st.a)) != CLEORA_OK) return rc;
         std::swap(y, ynext);
     }
     // E_T = whiten(Y_{T-1})
@@ -1145,6 +1176,10 @@ static int embed_impl(const cleora_graph *g, const uint64_t *entity_hash_host, c
     const bool f16 = (flags & CLEORA_F_ITERATE_F16) != 0;
     CL_REQUIRE(!(f16 && (flags & CLEORA_F_WHITEN)), "ITERATE_F16 is for the plain loop: the whitening kernels read f32 iterates");
     CL_REQUIRE(!f16 || (d % 4 == 0 && d <= 2048), "ITERATE_F16: d must be a multiple of 4, at most 2048");
+    const bool gather16 = (flags & CLEORA_F_GATHER_F16) != 0;
+    CL_REQUIRE(!gather16 || (flags & CLEORA_F_WHITEN), "GATHER_F16 is for the whitened loop (CLEORA_F_WHITEN); the plain loop has ITERATE_F16");
+    CL_REQUIRE(!gather16 || !(convergence_threshold > 0.0f), "GATHER_F16: the loop with a convergence threshold keeps the reference's order and gathers f32");
+    CL_REQUIRE(!gather16 || (d % 4 == 0 && d <= 2048), "GATHER_F16: d must be a multiple of 4, at most 2048");
     CL_HIP(hipSetDevice(g->device));
     auto emit = [&](const float *result, uint64_t nbytes) -> int {
         if (x_dev) {
@@ -1186,8 +1221,10 @@ static int embed_impl(const cleora_graph *g, const uint64_t *entity_hash_host, c
     if (whitened) {
         float *result = nullptr;
         if (overlapped) {
+            DevBuf yh;                                     // the f16 gather copy: a plain allocation, no placement search
+            if (gather16 && max_iterations > 1 && (rc = yh.alloc(bytes / 2)) != CLEORA_OK) return rc;
             rc = embed_whitened_overlapped(g, b.as<float>(), a.as<float>(), c.as<float>(), markov_type, d, max_iterations,
-                                           residual_weight, flags, &result);
+                                           residual_weight, flags, &result, yh.as<uint16_t>());
             if (rc == CLEORA_OK && iterations_run) *iterations_run = max_iterations;
         } else {
             rc = embed_whitened(g, a.as<float>(), b.as<float>(), c.as<float>(), markov_type, d, max_iterations,

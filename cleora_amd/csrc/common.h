@@ -127,6 +127,9 @@ int ensure_hub_partial(const cleora_graph *g, uint32_t d, bool segmented, hipStr
 // spmm_h.hip: the same SpMM on f16-stored x / x_self / y (f32 in between; long rows always segmented)
 int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, uint16_t *y, uint64_t ldy,
                        uint32_t flags, float rw, const uint16_t *x_self, double *row_sqdiff, hipStream_t stream);
+// ... and with an f32 y: the f16 gather of the whitened loop (flags: L2NORM / L1NORM / FASTNORM; nothing is rounded on the way out)
+int launch_propagate_hf(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, float *y, uint64_t ldy,
+                        uint32_t flags, hipStream_t stream);
 // hot.hip
 const uint32_t *ensure_hot_cols(const cleora_graph *g, uint32_t d, uint64_t ldx, hipStream_t stream,
                                 uint32_t elem_size = sizeof(float));   // bytes per stored element: the hot set is sized by row bytes
@@ -167,7 +170,8 @@ int launch_project(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const f
 // product, the transform resident in registers; the whitened loop's intermediate iterations
 bool project_f16_applies(const float *x, uint64_t ldx, uint64_t n, uint32_t d, uint32_t k, const float *out, uint64_t ldo, const float *x2);
 int launch_project_f16(const float *x, uint64_t ldx, uint64_t n, const float *mean, const float *t, float *out, uint64_t ldo,
-                       hipStream_t stream, const float *rowscale, const float *rowbound, int norm);
+                       hipStream_t stream, const float *rowscale, const float *rowbound, int norm,
+                       uint16_t *out_h = nullptr, uint64_t ldo_h = 0);   // out_h (norm 1 / 2 only): the same rows once more, rounded to f16
 
 // similarity.hip
 uint64_t topk_workspace_bytes(uint64_t n, uint32_t k, uint32_t n_queries);

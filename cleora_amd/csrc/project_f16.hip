@@ -38,6 +38,11 @@
 // them — the epilogue pipelined into the next tile's MFMAs (32-row tiles), the two waves of a SIMD in opposite phases, row-major
 // read-back through LDS for whole-line stores — measured 4.8 / 5.5 / no gain (same file).  The first form of this kernel (accumulators
 // staged through LDS for a row-major pass, two barriers per tile) ran 5.3-5.45 ms.
+//
+// COPY variant (CLEORA_F_GATHER_F16): the same kernel also stores every output row a second time, rounded to f16 (to
+// nearest even) — the operand the next SpMM gathers at half the bytes (spmm_h.hip).  Its instantiations live in a translation unit of
+// their own, project_f16_copy.hip, which includes this file with PF_COPY_TU defined and is compiled without packed f32 arithmetic;
+// this file's own object keeps the kernels, the flags and the code it had.
 #include <type_traits>
 
 #include "common.h"
@@ -101,16 +106,23 @@ __device__ __forceinline__ void pf_barrier() {                 // LDS-only hand-
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-struct F16Args {
+}  // namespace
+
+struct F16Args {                // (named: it crosses to project_f16_copy.hip)
     ProjArgs p;
     const u32x4 *tp;
     const float *colscale;
     const float *rowscale;     // per row s_r (never null: the launcher passes ones)
     const float *rowbound;     // per row B_r (never null)
     uint64_t full_blocks;      // blocks sharing the full tiles (gridDim.x minus the ragged tile's block)
+    uint16_t *out_h;           // COPY kernels: the f16 copy of out, ldo_h halfs per row
+    uint64_t ldo_h;
 };
+int launch_project_f16_copy(const F16Args &a, unsigned grid, int norm, hipStream_t stream);    // project_f16_copy.hip
 
-template <int NORM>
+namespace {
+
+template <int NORM, bool COPY = false>
 __global__ __launch_bounds__(PF_THREADS, 2) void project_f16_kernel(const F16Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *const frag = smem;                                             // [2][PF_BUF]
@@ -314,6 +326,23 @@ __global__ __launch_bounds__(PF_THREADS, 2) void project_f16_kernel(const F16Arg
                     if (!LAST || row0 + 16 * u < p.n)
                         *reinterpret_cast<float4 *>(orow + (uint64_t)(16 * u) * p.ldo + 16 * g) = v;
                 }
+            if constexpr (COPY) {
+                // the f16 copy, from the SAME o[] the f32 stores took: each value rounded to nearest even (v_cvt_f16_f32, never the
+                // round-toward-zero pack), a lane's four columns as one 8-byte store — a 16-lane row writes 32 contiguous bytes of one
+                // matrix row, an instruction 16 rows.  (16-byte stores would take another lane exchange: DESIGN.md §2.4.)
+                typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+                uint16_t *const hrow = a.out_h + row0 * a.ldo_h + 32 * w + 4 * (lane >> 4);
+#pragma unroll
+                for (int g = 0; g < 2; ++g)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const h2v lo = {(_Float16)o[8 * g + 4 * u], (_Float16)o[8 * g + 4 * u + 1]};
+                        const h2v hi = {(_Float16)o[8 * g + 4 * u + 2], (_Float16)o[8 * g + 4 * u + 3]};
+                        if (!LAST || row0 + 16 * u < p.n)
+                            *reinterpret_cast<uint2 *>(hrow + (uint64_t)(16 * u) * a.ldo_h + 16 * g) =
+                                make_uint2(__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi));
+                    }
+            }
         }
     };
     if (ragged) {
@@ -336,6 +365,20 @@ __global__ __launch_bounds__(256) void fill_ones_kernel(float *__restrict__ v, u
 
 }  // namespace
 
+#ifdef PF_COPY_TU
+// the COPY kernels' launch (norm 1 / 2: a gather copy is a copy of normalised rows), arguments prepared by launch_project_f16
+int launch_project_f16_copy(const F16Args &a, unsigned grid, int norm, hipStream_t stream) {
+    auto go = [&](auto kernel) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS);
+        if (e == hipSuccess) hipLaunchKernelGGL(kernel, dim3(grid), dim3(PF_THREADS), PF_LDS, stream, a);
+        return e;
+    };
+    const hipError_t e = norm == 1 ? go(project_f16_kernel<1, true>) : go(project_f16_kernel<2, true>);
+    CL_HIP(e != hipSuccess ? e : hipGetLastError());
+    return CLEORA_OK;
+}
+#else
+
 bool project_f16_applies(const float *x, uint64_t ldx, uint64_t n, uint32_t d, uint32_t k, const float *out, uint64_t ldo, const float *x2) {
     auto aligned16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
     return d == PF_D && k == PF_D && x2 == nullptr && n >= 1 && ldx % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(out) &&
@@ -344,10 +387,17 @@ bool project_f16_applies(const float *x, uint64_t ldx, uint64_t n, uint32_t d, u
 
 // out = normalise((x - rowscale (x) mean) T) for BOUNDED operands: |x[r][j]| <= rowbound[r] (nullptr: 1), |mean[j]| <= 1.
 // norm: 0 none, 1 L2, 2 L1 (always applied in the epilogue: whole rows live in one block).
+// out_h != nullptr (norm 1 / 2): every row is also stored rounded to f16, ldo_h halfs apart (the COPY kernels).
 int launch_project_f16(const float *x, uint64_t ldx, uint64_t n, const float *mean, const float *t, float *out, uint64_t ldo,
-                       hipStream_t stream, const float *rowscale, const float *rowbound, int norm) {
+                       hipStream_t stream, const float *rowscale, const float *rowbound, int norm, uint16_t *out_h, uint64_t ldo_h) {
     CL_REQUIRE(project_f16_applies(x, ldx, n, PF_D, PF_D, out, ldo, nullptr), "internal: the f16 projection does not apply to this shape");
     CL_REQUIRE(mean != nullptr && t != nullptr, "mean / transform is NULL");
+    if (out_h) {
+        CL_REQUIRE(norm == 1 || norm == 2, "the f16 copy is a copy of normalised rows: norm must be 1 or 2");
+        CL_REQUIRE(ldo_h >= PF_D && ldo_h % 4 == 0 && ldo_h < (1u << 24) && (reinterpret_cast<uintptr_t>(out_h) & 7u) == 0,
+                   "out_h: 8-byte aligned, ldo_h a multiple of 4, at least 256");
+        CL_REQUIRE((const void *)out_h != (const void *)x && (const void *)out_h != (const void *)out, "out_h must not alias x / out");
+    }
     _Float16 *tp = nullptr;
     float *colscale = nullptr;
     CL_HIP(hipMallocAsync(reinterpret_cast<void **>(&tp), (size_t)PF_D * PF_D * 2 * sizeof(_Float16) + PF_D * sizeof(float), stream));
@@ -382,19 +432,24 @@ int launch_project_f16(const float *x, uint64_t ldx, uint64_t n, const float *me
     a.rowbound = rowbound ? rowbound : ones;
     const uint64_t tiles_full = n / PF_ROWS;
     a.full_blocks = tiles_full < (uint64_t)cus ? tiles_full : (uint64_t)cus;
+    a.out_h = out_h;
+    a.ldo_h = ldo_h;
     const unsigned gt = (unsigned)a.full_blocks + (n % PF_ROWS ? 1u : 0u);          // + the ragged tile's block
     auto go = [&](auto kernel) {
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS);
         if (e == hipSuccess) hipLaunchKernelGGL(kernel, dim3(gt), dim3(PF_THREADS), PF_LDS, stream, a);
     };
-    if (norm == 1) go(project_f16_kernel<1>);
+    int rc = CLEORA_OK;
+    if (out_h) rc = launch_project_f16_copy(a, gt, norm, stream);
+    else if (norm == 1) go(project_f16_kernel<1>);
     else if (norm == 2) go(project_f16_kernel<2>);
     else go(project_f16_kernel<0>);
     const hipError_t le = e != hipSuccess ? e : hipGetLastError();
     if (ones) CL_HIP(hipFreeAsync(ones, stream));
     CL_HIP(hipFreeAsync(tp, stream));
     CL_HIP(le);
-    return CLEORA_OK;
+    return rc;
 }
+#endif  // PF_COPY_TU
 
 }  // namespace cleora

@@ -24,6 +24,10 @@
 //   * rows longer than hub_threshold ALWAYS take the segmented schedule (what CLEORA_F_HUB_SEGMENTS selects in spmm.hip): their
 //     hub_segment-edge segments are the first work items, f32 partial sums go to the graph's hub_partial scratch and
 //     hub_finish_h_kernel adds them in a fixed order and runs the epilogue.  In-order f16 hub kernels are a follow-up.
+//
+// F32OUT variant (cleora_propagate_hf_dev; CLEORA_F_GATHER_F16 in the whitened loop): the same gather on an f16 X, but Y is f32 and
+// nothing is rounded on the way out — the loop's Z = A Y, whose input rows are normalised (|Y| <= 1) and whose output the projection
+// consumes in f32.  Same contract up to the epilogue (L2 / L1 / FASTNORM; no x_self flags); tests/test_gpu_gather_f16.py.
 #include "common.h"
 #include "row_epilogue.h"
 
@@ -58,6 +62,7 @@ struct SpmmHArgs {
     const uint16_t *x_self;
     uint64_t ldxs;
     RowArgs r;             // flags, rw / alpha, d, row_sqdiff (its f32 pointers are not used)
+    float *y32;            // the f32 output of the F32OUT kernels (y is not used there); ldy counts its elements
 };
 
 __device__ __forceinline__ float widen_lo(uint32_t t) { return (float)__builtin_bit_cast(f16x2, t).x; }
@@ -211,10 +216,38 @@ __device__ __forceinline__ void finish_row_h(const SpmmHArgs &a, uint64_t row, i
     }
 }
 
+// The row epilogue of the f16-gather / f32-output kernels (the whitened loop's Z = A Y, consumed in f32 by the projection): the f32
+// arithmetic of row_epilogue.h on the sums and NO rounding — the accumulators leave as they are.  A lane's C consecutive columns are
+// C / 4 16-byte stores: at C = 4 a store instruction writes 1 KiB of the row contiguously; at C = 8 (rows >= 1 KiB) the lane's two
+// stores are 16 bytes apart and the lanes 32 bytes, so each instruction writes every other 16-byte piece of 2 KiB and the pair
+// completes the lines (back to back from one wave).  No x_self: RESIDUAL / SQDIFF are refused by the launcher.
+template <int G, int V, int C>
+__device__ __forceinline__ void finish_row_hf(const SpmmHArgs &a, uint64_t row, int gl, int gbase, float (&acc)[V][C]) {
+    const RowArgs &ra = a.r;
+    const uint32_t d = ra.d;
+    float xs[V][C];                                                   // never read: RESIDUAL is not set
+    blend_and_normalize<G, V, C>(ra, row, gl, gbase, acc, xs);
+    typedef float nt_f4 __attribute__((ext_vector_type(4)));
+    float *yr = a.y32 + row * a.ldy;
+    const bool nt = (ra.flags & kStreamStores) != 0;                  // streaming store: see kStreamStores
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const uint32_t j = (uint32_t)(v * G + gl) * C;
+        if (j < d) {                                                  // (C = 8 only where d % 8 == 0: whole chunks)
+#pragma unroll
+            for (int q = 0; q < C; q += 4) {
+                const nt_f4 o = {acc[v][q], acc[v][q + 1], acc[v][q + 2], acc[v][q + 3]};
+                if (nt) __builtin_nontemporal_store(o, reinterpret_cast<nt_f4 *>(yr + j + q));
+                else *reinterpret_cast<nt_f4 *>(yr + j + q) = o;
+            }
+        }
+    }
+}
+
 // ---- main kernel ---------------------------------------------------------------------------
 // Work items: first the hub SEGMENTS (so the longest work starts first), then one item per row.  A segment item writes its f32
-// partial sum to scratch; a row item runs the epilogue and writes Y.
-template <int G, int V, int C, bool HOT>
+// partial sum to scratch; a row item runs the epilogue and writes Y (f16, or f32 with F32OUT).
+template <int G, int V, int C, bool HOT, bool F32OUT = false>
 __global__ __launch_bounds__(256) void spmm_rows_h_kernel(const SpmmHArgs a) {
     const int lane = threadIdx.x & 63;
     const int gl = lane & (G - 1);
@@ -266,6 +299,8 @@ __global__ __launch_bounds__(256) void spmm_rows_h_kernel(const SpmmHArgs a) {
                     *reinterpret_cast<float4 *>(p + j + q) = make_float4(acc[v][q], acc[v][q + 1], acc[v][q + 2], acc[v][q + 3]);
             }
         }
+    } else if constexpr (F32OUT) {
+        finish_row_hf<G, V, C>(a, row, gl, gbase, acc);
     } else {
         finish_row_h<G, V, C>(a, row, gl, gbase, acc);
     }
@@ -274,7 +309,7 @@ __global__ __launch_bounds__(256) void spmm_rows_h_kernel(const SpmmHArgs a) {
 // ---- hub rows: in-order combine of the segment partials + epilogue -----------------------------
 // hub_finish_kernel of spmm.hip with the f16 epilogue: one 256-thread block per hub row, four wavefronts each adding a contiguous
 // run of the row's segments in order (8 loads in flight), the four sums added in wave order through LDS.  Fixed order => deterministic.
-template <int V>
+template <int V, bool F32OUT = false>
 __global__ __launch_bounds__(256) void hub_finish_h_kernel(const SpmmHArgs a) {
     __shared__ float sm[4][64 * V * 4];
     const int gl = threadIdx.x & 63;
@@ -323,7 +358,8 @@ __global__ __launch_bounds__(256) void hub_finish_h_kernel(const SpmmHArgs a) {
         for (int v = 0; v < V; ++v)
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[v][q] = fadd(acc[v][q], sm[g2][(v * 64 + gl) * 4 + q]);
-    finish_row_h<64, V, 4>(a, row, gl, 0, acc);
+    if constexpr (F32OUT) finish_row_hf<64, V, 4>(a, row, gl, 0, acc);
+    else finish_row_h<64, V, 4>(a, row, gl, 0, acc);
 }
 
 // ---- shape dispatch -----------------------------------------------------------------------------
@@ -352,27 +388,10 @@ inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<ui
 
 }  // namespace
 
-int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, uint16_t *y, uint64_t ldy,
-                       uint32_t flags, float rw, const uint16_t *x_self, double *row_sqdiff, hipStream_t stream) {
-    CL_REQUIRE(g != nullptr, "graph handle is NULL");
-    CL_REQUIRE(kind == CLEORA_LEFT || kind == CLEORA_SYMMETRIC, "unknown markov_type");
-    CL_REQUIRE(g->val[kind] != nullptr, "graph has no values for this markov_type");
-    CL_REQUIRE(d > 0 && ldx >= d && ldy >= d, "bad d / leading dimension");
-    CL_REQUIRE(x != nullptr && y != nullptr, "x / y is NULL");
-    CL_REQUIRE(x != y, "x and y must not alias");
-    CL_REQUIRE(d % 4 == 0 && d <= kMaxDH, "f16 rows: d must be a multiple of 4, at most 2048");
-    CL_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "f16 rows: leading dimensions must be multiples of 4");
-    CL_REQUIRE(!(flags & (CLEORA_F_ROWSQ | CLEORA_F_SCALE | CLEORA_F_ROWSQ_CONT)), "f16 rows: ROWSQ / SCALE / ROWSQ_CONT are not served");
-    CL_REQUIRE(!((flags & CLEORA_F_L1NORM) && (flags & CLEORA_F_L2NORM)), "L1NORM is exclusive with L2NORM");
-    if ((flags & CLEORA_F_RESIDUAL) && !(rw > 0.0f && (rw < 1.0f || (flags & CLEORA_F_BLEND_ANY)))) flags &= ~CLEORA_F_RESIDUAL;
-    if (flags & (CLEORA_F_RESIDUAL | CLEORA_F_SQDIFF)) {
-        if (!x_self && g->n_rows == g->n_cols) x_self = x;
-        CL_REQUIRE(x_self != nullptr, "x_self is required for RESIDUAL / SQDIFF on a row shard");
-    }
-    CL_REQUIRE(aligned_to(x, 8) && aligned_to(y, 8) && (!x_self || aligned_to(x_self, 8)), "f16 rows: x / y / x_self must be 8-byte aligned");
-    if (flags & CLEORA_F_SQDIFF) CL_REQUIRE(row_sqdiff != nullptr, "row_sqdiff is NULL");
-    if (g->n_rows == 0) return CLEORA_OK;
-
+// The launches behind both entry points, arguments checked: y is uint16_t[n_rows][ldy], or float[n_rows][ldy] with F32OUT.
+template <bool F32OUT>
+static int launch_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, void *y, uint64_t ldy, uint32_t flags,
+                    float rw, const uint16_t *x_self, double *row_sqdiff, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(g->mu);
     CL_HIP(hipSetDevice(g->device));
     flags &= ~CLEORA_F_HUB_SEGMENTS;                       // implied: long rows always take the segmented schedule here
@@ -397,17 +416,20 @@ int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint6
     a.hub_rows = g->hub_rows;
     a.hub_seg_first = g->hub_seg_first;
     a.partial = g->hub_partial;
-    a.y = y;
+    if constexpr (F32OUT) a.y32 = static_cast<float *>(y);
+    else a.y = static_cast<uint16_t *>(y);
     a.ldy = ldy;
     a.x_self = x_self;
     a.ldxs = ldx;
     a.r.row_sqdiff = row_sqdiff;
     a.r.rw = rw;
     a.r.alpha = 1.0f - rw;
-    a.r.flags = flags | (g->n_rows * ldy * sizeof(uint16_t) >= kStreamStoreMinBytes ? kStreamStores : 0u);
+    const uint64_t y_bytes = g->n_rows * ldy * (F32OUT ? sizeof(float) : sizeof(uint16_t));
+    a.r.flags = flags | (y_bytes >= kStreamStoreMinBytes ? kStreamStores : 0u);
     a.r.d = d;
 
-    const bool wide = d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && aligned_to(x, 16) && aligned_to(y, 16) &&
+    // 16-byte gathers: the f16 operands 16-byte aligned (an f32 y always is: its launcher requires it)
+    const bool wide = d % 8 == 0 && ldx % 8 == 0 && aligned_to(x, 16) && (F32OUT || (ldy % 8 == 0 && aligned_to(y, 16))) &&
                       (!x_self || aligned_to(x_self, 16));
     dispatch_shape_h(d, wide, [&](auto G, auto V, auto C) {
         constexpr int kG = decltype(G)::value, kV = decltype(V)::value, kC = decltype(C)::value;
@@ -418,20 +440,62 @@ int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint6
         if (hot) {
             SpmmHArgs h = a;
             h.col = hot;
-            hipLaunchKernelGGL((spmm_rows_h_kernel<kG, kV, kC, true>), grid, dim3(256), 0, stream, h);
+            hipLaunchKernelGGL((spmm_rows_h_kernel<kG, kV, kC, true, F32OUT>), grid, dim3(256), 0, stream, h);
         } else {
-            hipLaunchKernelGGL((spmm_rows_h_kernel<kG, kV, kC, false>), grid, dim3(256), 0, stream, a);
+            hipLaunchKernelGGL((spmm_rows_h_kernel<kG, kV, kC, false, F32OUT>), grid, dim3(256), 0, stream, a);
         }
     });
     if (g->n_hub_rows) {
         const dim3 grid((unsigned)g->n_hub_rows);
-        if (d <= 256) hipLaunchKernelGGL(hub_finish_h_kernel<1>, grid, dim3(256), 0, stream, a);
-        else if (d <= 512) hipLaunchKernelGGL(hub_finish_h_kernel<2>, grid, dim3(256), 0, stream, a);
-        else if (d <= 1024) hipLaunchKernelGGL(hub_finish_h_kernel<4>, grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(hub_finish_h_kernel<8>, grid, dim3(256), 0, stream, a);
+        if (d <= 256) hipLaunchKernelGGL((hub_finish_h_kernel<1, F32OUT>), grid, dim3(256), 0, stream, a);
+        else if (d <= 512) hipLaunchKernelGGL((hub_finish_h_kernel<2, F32OUT>), grid, dim3(256), 0, stream, a);
+        else if (d <= 1024) hipLaunchKernelGGL((hub_finish_h_kernel<4, F32OUT>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((hub_finish_h_kernel<8, F32OUT>), grid, dim3(256), 0, stream, a);
     }
     CL_HIP(hipGetLastError());
     return CLEORA_OK;
+}
+
+int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, uint16_t *y, uint64_t ldy,
+                       uint32_t flags, float rw, const uint16_t *x_self, double *row_sqdiff, hipStream_t stream) {
+    CL_REQUIRE(g != nullptr, "graph handle is NULL");
+    CL_REQUIRE(kind == CLEORA_LEFT || kind == CLEORA_SYMMETRIC, "unknown markov_type");
+    CL_REQUIRE(g->val[kind] != nullptr, "graph has no values for this markov_type");
+    CL_REQUIRE(d > 0 && ldx >= d && ldy >= d, "bad d / leading dimension");
+    CL_REQUIRE(x != nullptr && y != nullptr, "x / y is NULL");
+    CL_REQUIRE(x != y, "x and y must not alias");
+    CL_REQUIRE(d % 4 == 0 && d <= kMaxDH, "f16 rows: d must be a multiple of 4, at most 2048");
+    CL_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "f16 rows: leading dimensions must be multiples of 4");
+    CL_REQUIRE(!(flags & (CLEORA_F_ROWSQ | CLEORA_F_SCALE | CLEORA_F_ROWSQ_CONT)), "f16 rows: ROWSQ / SCALE / ROWSQ_CONT are not served");
+    CL_REQUIRE(!((flags & CLEORA_F_L1NORM) && (flags & CLEORA_F_L2NORM)), "L1NORM is exclusive with L2NORM");
+    if ((flags & CLEORA_F_RESIDUAL) && !(rw > 0.0f && (rw < 1.0f || (flags & CLEORA_F_BLEND_ANY)))) flags &= ~CLEORA_F_RESIDUAL;
+    if (flags & (CLEORA_F_RESIDUAL | CLEORA_F_SQDIFF)) {
+        if (!x_self && g->n_rows == g->n_cols) x_self = x;
+        CL_REQUIRE(x_self != nullptr, "x_self is required for RESIDUAL / SQDIFF on a row shard");
+    }
+    CL_REQUIRE(aligned_to(x, 8) && aligned_to(y, 8) && (!x_self || aligned_to(x_self, 8)), "f16 rows: x / y / x_self must be 8-byte aligned");
+    if (flags & CLEORA_F_SQDIFF) CL_REQUIRE(row_sqdiff != nullptr, "row_sqdiff is NULL");
+    if (g->n_rows == 0) return CLEORA_OK;
+    return launch_h<false>(g, kind, x, ldx, d, y, ldy, flags, rw, x_self, row_sqdiff, stream);
+}
+
+// y (f32) = epilogue(A widen(x)): the gather of launch_propagate_h, nothing rounded on the way out.  flags: L2NORM / L1NORM / FASTNORM.
+int launch_propagate_hf(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, float *y, uint64_t ldy,
+                        uint32_t flags, hipStream_t stream) {
+    CL_REQUIRE(g != nullptr, "graph handle is NULL");
+    CL_REQUIRE(kind == CLEORA_LEFT || kind == CLEORA_SYMMETRIC, "unknown markov_type");
+    CL_REQUIRE(g->val[kind] != nullptr, "graph has no values for this markov_type");
+    CL_REQUIRE(d > 0 && ldx >= d && ldy >= d, "bad d / leading dimension");
+    CL_REQUIRE(x != nullptr && y != nullptr, "x / y is NULL");
+    CL_REQUIRE((const void *)x != (const void *)y, "x and y must not alias");
+    CL_REQUIRE(d % 4 == 0 && d <= kMaxDH, "f16 gather: d must be a multiple of 4, at most 2048");
+    CL_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "f16 gather: leading dimensions must be multiples of 4");
+    CL_REQUIRE(!(flags & (CLEORA_F_RESIDUAL | CLEORA_F_SQDIFF | CLEORA_F_ROWSQ | CLEORA_F_SCALE | CLEORA_F_ROWSQ_CONT)),
+               "f16 gather into f32 rows: RESIDUAL / SQDIFF / ROWSQ / SCALE / ROWSQ_CONT are not served");
+    CL_REQUIRE(!((flags & CLEORA_F_L1NORM) && (flags & CLEORA_F_L2NORM)), "L1NORM is exclusive with L2NORM");
+    CL_REQUIRE(aligned_to(x, 8) && aligned_to(y, 16), "f16 gather: x must be 8-byte, y 16-byte aligned");
+    if (g->n_rows == 0) return CLEORA_OK;
+    return launch_h<true>(g, kind, x, ldx, d, y, ldy, flags, 0.0f, nullptr, nullptr, stream);
 }
 
 }  // namespace cleora

@@ -153,6 +153,9 @@ def embed(graph, feature_dim=DEFAULT_FEATURE_DIM, num_iterations=DEFAULT_NUM_ITE
             m = graph._multi()
             if m is not None:                        # several devices configured (cleora_amd.install(devices=...)): the row partition
                 return m.embed(hashes, x0, kind, d, int(num_iterations), int(seed), float(residual_weight), float(max(convergence_threshold, 0.0)), flags)[0]
+            # install(gather_dtype="f16"): a preference — only the reorganised loop (no threshold) at the widths the f16 gather serves
+            if _pyc.gather_f16() and not convergence_threshold > 0 and d % 4 == 0 and d <= 2048:
+                flags |= _hip.F_GATHER_F16
             _hip.check(L.cleora_embed(graph._graph().handle, _hip.ptr(hashes), _hip.ptr(x0), kind, d, int(num_iterations), int(seed),
                                       float(residual_weight), float(max(convergence_threshold, 0.0)), flags,
                                       _hip.ptr(out), ctypes.byref(ran)))

@@ -63,6 +63,24 @@ def set_iterate_dtype(dtype):
     _ITERATE_F16 = dtype == "f16"
 
 
+_GATHER_F16 = False     # set by cleora_amd.install(gather_dtype=...)
+
+
+def set_gather_dtype(dtype):
+    """What the SpMMs of the whitened one-call loop of cleora_amd.embed.embed() gather on the one-GPU path: "f32" (default) or "f16"
+    (CLEORA_F_GATHER_F16: an f16 copy of the normalised rows, half the gathered bytes, f32 sums and statistics; not the reference's
+    bits).  A preference: calls that do not qualify (a convergence threshold, a callback, several devices, d % 4 != 0 or d > 2048)
+    run in f32."""
+    global _GATHER_F16
+    if dtype not in ("f16", "f32"):
+        raise ValueError(f"gather_dtype must be 'f16' or 'f32', got {dtype!r}")
+    _GATHER_F16 = dtype == "f16"
+
+
+def gather_f16():
+    return _GATHER_F16
+
+
 def loop_flags():
     on = _HUB_SEGMENTS if _HUB_SEGMENTS is not None else os.environ.get("CLEORA_HUB_SEGMENTS", "").strip() not in ("", "0")
     return _hip.F_HUB_SEGMENTS if on else 0

@@ -77,6 +77,9 @@ extern "C" {
                                    * for bit (csrc/colsharded.hip) */
 #define CLEORA_F_ITERATE_F16 4096u /* cleora_embed / cleora_embed_dev, plain loop only: the iterates are STORED as IEEE binary16 between
                                     * iterations (cleora_propagate_h_dev).  Opt-in and not the reference's bits; see cleora_embed */
+#define CLEORA_F_GATHER_F16 8192u  /* cleora_embed / cleora_embed_dev with CLEORA_F_WHITEN and no convergence threshold: every SpMM after
+                                    * the first GATHERS an f16 copy of the normalised rows (cleora_propagate_hf_dev); sums, statistics
+                                    * and projections stay f32.  Opt-in and not the reference's bits; see cleora_embed */
 
 typedef struct cleora_graph cleora_graph; /* device-resident CSR shard (struct SparseMatrix, src/sparse_matrix.rs:56-78) */
 
@@ -217,6 +220,14 @@ int cleora_propagate_h_dev(const cleora_graph *g, int markov_type, const uint16_
                            uint64_t ldy, uint32_t flags, float residual_weight, const uint16_t *x_self_h, double *row_sqdiff,
                            void *stream);
 
+/* The f16 GATHER alone (csrc/spmm_h.hip): x_h holds IEEE binary16 bits, y_f32 is f32.  The gather, the widening, the separate f32
+ * multiply and add in stored edge order and the segmented long rows are those of cleora_propagate_h_dev; the epilogue (flags:
+ * L2NORM or L1NORM, FASTNORM) runs on the f32 sums and the result is stored with NO rounding.  RESIDUAL, SQDIFF, ROWSQ, SCALE and
+ * ROWSQ_CONT are CLEORA_E_INVALID.  d % 4 == 0, d <= 2048, ldx % 4 == 0 and x_h 8-byte aligned; y_f32 16-byte aligned with
+ * ldy % 4 == 0.  What the whitened loop runs under CLEORA_F_GATHER_F16: x_h = the rounded copy of the normalised rows Y. */
+int cleora_propagate_hf_dev(const cleora_graph *g, int markov_type, const uint16_t *x_h, uint64_t ldx, uint32_t d, float *y_f32,
+                            uint64_t ldy, uint32_t flags, void *stream);
+
 /* Storage conversion of an n x d matrix: f32 -> f16 rounds to nearest even and keeps subnormals, f16 -> f32 is exact. */
 int cleora_convert_f32_to_f16_dev(const float *src, uint64_t ld_src, uint64_t n, uint32_t d, uint16_t *dst, uint64_t ld_dst, void *stream);
 int cleora_convert_f16_to_f32_dev(const uint16_t *src, uint64_t ld_src, uint64_t n, uint32_t d, float *dst, uint64_t ld_dst, void *stream);
@@ -314,6 +325,15 @@ int cleora_csr_rowsums_dev(const cleora_graph *g, int markov_type, float *rowsum
 int cleora_project_bounded_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *mean_f32_dev,
                                const float *transform_dev, uint32_t k, float *out, uint64_t ldo, const float *rowscale_dev,
                                const float *rowbound_dev, int norm, int *norm_done, int *form, void *stream);
+
+/* cleora_project_bounded_dev where its f16 form applies (d = k = 256, 16-byte-aligned rows: CLEORA_E_INVALID elsewhere) and norm
+ * is 1 or 2, with a SECOND output: out_h[r][j] = the f16 nearest (ties to even) to the out[r][j] the call stores, ldo_h halfs per row
+ * (ldo_h % 4 == 0, out_h 8-byte aligned), written by the same kernel's epilogue.  out is bit-identical to
+ * cleora_project_bounded_dev's.  The operand of cleora_propagate_hf_dev in the next iteration of the whitened loop. */
+int cleora_project_bounded_h_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *mean_f32_dev,
+                                 const float *transform_dev, uint32_t k, float *out, uint64_t ldo, const float *rowscale_dev,
+                                 const float *rowbound_dev, int norm, int *norm_done, int *form, uint16_t *out_h, uint64_t ldo_h,
+                                 void *stream);
 
 /* mean64[c] = colsum[c] / n (f64, :136) and mean32[c] = (float)mean64[c] (:159), on the device. */
 int cleora_mean_dev(const double *colsum_dev, uint64_t n, uint32_t d, double *mean64_dev,
@@ -649,7 +669,14 @@ int cleora_whiten(const float *x_host, uint64_t n, uint32_t d, uint32_t n_compon
  * fixed order — the RMSE of the f16 iterates the loop holds), and the result is widened into the f32 output (cleora_embed_dev keeps
  * its f32 in / out buffer).  Rows need d % 4 == 0, d <= 2048.  Long rows take the segmented sum.  The placement search is skipped
  * for the f16 buffers.  Together with CLEORA_F_WHITEN the flag is CLEORA_E_INVALID (the whitening kernels read f32), and so it is
- * in cleora_embed_sharded, cleora_embed_colsharded and cleora_multi_embed. */
+ * in cleora_embed_sharded, cleora_embed_colsharded and cleora_multi_embed.
+ * With CLEORA_F_GATHER_F16 the reorganised WHITENED loop keeps one extra n x d f16 buffer: the normalised rows Y rounded to nearest
+ * even (|Y| <= 1).  Every SpMM from the second on gathers that copy (cleora_propagate_hf_dev: exact widening, f32 sums, f32 Z);
+ * the first (A E_0: unbounded user data), the statistics, the d x d step, the projections and the final whitening read f32 as
+ * before.  At d = 256 without a blend the copy leaves the projection's own epilogue (cleora_project_bounded_h_dev); every other
+ * producer of Y is followed by one conversion pass.  Long rows take the segmented sum.  Needs CLEORA_F_WHITEN, no convergence
+ * threshold, d % 4 == 0, d <= 2048: CLEORA_E_INVALID otherwise, and in cleora_embed_sharded, cleora_embed_colsharded and
+ * cleora_multi_embed.  Not the reference's bits: pairwise cosines move by the rounding of Y (about 1e-4 after a few iterations). */
 int cleora_embed(const cleora_graph *g, const uint64_t *entity_hash_host, const float *x0_host,
                  int markov_type, uint32_t d, uint64_t max_iterations, int64_t seed,
                  float residual_weight, float convergence_threshold, uint32_t flags,
