@@ -9,7 +9,7 @@
 __version__ = "0.1.0"
 
 
-def install(devices=None, hub_segments=None, iterate_dtype=None, gather_dtype=None):
+def install(devices=None, hub_segments=None, iterate_dtype=None, gather_dtype=None, stats_dtype=None):
     """Make this package's SparseMatrix the reference's compiled module: after this call
     `import pycleora` (the reference's unmodified Python package) binds
     `from .pycleora import SparseMatrix` (pycleora/__init__.py:4) to cleora_amd.pycleora.
@@ -26,7 +26,11 @@ def install(devices=None, hub_segments=None, iterate_dtype=None, gather_dtype=No
     gather_dtype: "f16" = the whitened one-call loop of cleora_amd.embed.embed() on one GPU gathers an f16 copy of its normalised rows
     in every SpMM after the first (CLEORA_F_GATHER_F16: half the gathered bytes; sums, statistics and projections stay f32; NOT the
     reference's bits).  A preference: calls with a convergence threshold or a callback run in f32 as before.  "f32" restores the
-    default; None keeps the current setting.  Not combinable with `devices`."""
+    default; None keeps the current setting.  Not combinable with `devices`.
+    stats_dtype: "f16" = with gather_dtype="f16", the loop keeps its intermediate normalised rows ONLY as f16 (CLEORA_F_STATS_F16:
+    statistics from the f16 matrix cores on the stored values, no f32 copy of the rows, one iterate-sized buffer fewer).  A preference
+    like gather_dtype: it also needs residual_weight == 0.  "f32" restores the default; None keeps the current setting.  Not
+    combinable with `devices`."""
     import importlib.util
     import sys
 
@@ -43,6 +47,12 @@ def install(devices=None, hub_segments=None, iterate_dtype=None, gather_dtype=No
         if devices is not None:
             raise ValueError("gather_dtype is served on one GPU only: do not combine it with devices=[...]")
         _mod.set_gather_dtype(gather_dtype)
+    if stats_dtype is not None:
+        if stats_dtype not in ("f16", "f32"):
+            raise ValueError(f"stats_dtype must be 'f16' or 'f32', got {stats_dtype!r}")
+        if devices is not None:
+            raise ValueError("stats_dtype is served on one GPU only: do not combine it with devices=[...]")
+        _mod.set_stats_dtype(stats_dtype)
     if devices is not None:
         _mod.set_devices(devices)
     if hub_segments is not None:

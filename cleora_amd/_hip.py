@@ -18,6 +18,7 @@ F_L2NORM, F_FASTNORM, F_RESIDUAL, F_SQDIFF, F_ROWSQ, F_SCALE, F_WHITEN = 1, 2, 4
 F_L1NORM, F_BLEND_ANY, F_SQDIFF64, F_HUB_SEGMENTS, F_ROWSQ_CONT = 128, 256, 512, 1024, 2048
 F_ITERATE_F16 = 4096
 F_GATHER_F16 = 8192
+F_STATS_F16 = 16384
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 ALLGATHER_RING, ALLGATHER_P2P, ALLGATHER_PEER = 0, 1, 2
@@ -155,6 +156,7 @@ SIGNATURES = {
     "cleora_eigh_workspace": (c_u64, [c_u32]),
     "cleora_whiten_transform_dev": (c_int, [vp, c_u64, c_u32, c_u32, vp, vp, vp, vp]),
     "cleora_whiten_stats_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_int, vp, vp, vp]),
+    "cleora_whiten_stats_h_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, vp, vp, vp]),
     "cleora_whiten_transform_any_dev": (c_int, [vp, c_u64, c_u32, vp, vp, vp, ctypes.POINTER(c_int)]),
     "cleora_whiten_workspace": (c_u64, [c_u64, c_u32]),
     "cleora_whiten_dev": (c_int, [vp, c_u64, c_u64, c_u32, c_u32, vp, c_u64, vp, vp, vp]),

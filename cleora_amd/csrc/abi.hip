@@ -641,9 +641,9 @@ int cleora_project_bounded_h_dev(const float *x, uint64_t ldx, uint64_t n, uint3
                                  const float *rowbound_dev, int norm, int *norm_done, int *form, uint16_t *out_h, uint64_t ldo_h,
                                  void *stream) {
     CL_REQUIRE(norm == 1 || norm == 2, "the f16 copy is a copy of normalised rows: norm must be 1 or 2");
+    if (out == nullptr) ldo = k;                           // only the f16 rows are stored
     CL_REQUIRE(d > 0 && k > 0 && ldx >= d && ldo >= k && ldo_h >= k, "bad d / k / leading dimension");
-    CL_REQUIRE(x != nullptr && mean_f32_dev != nullptr && transform_dev != nullptr && out != nullptr && out_h != nullptr,
-               "x / mean / transform / out / out_h is NULL");
+    CL_REQUIRE(x != nullptr && mean_f32_dev != nullptr && transform_dev != nullptr && out_h != nullptr, "x / mean / transform / out_h is NULL");
     CL_REQUIRE((const void *)x != (const void *)out, "x and out must not alias");
     CL_REQUIRE(n > 0 && project_f16_applies(x, ldx, n, d, k, out, ldo, nullptr),
                "the projection with an f16 copy is served where the f16 form applies: d = k = 256, 16-byte aligned rows");
@@ -663,6 +663,16 @@ int cleora_whiten_stats_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d
                             double *mean64_dev, double *gram_dev, void *stream) {
     CL_REQUIRE(mean64_dev != nullptr && gram_dev != nullptr, "mean / gram is NULL");
     const int rc = launch_whiten_fit_stats(x, ldx, n, d, workspace, S(stream), 2, intermediate != 0);
+    if (rc != CLEORA_OK) return rc;
+    return whiten_fit_copy_stats(workspace, n, d, mean64_dev, gram_dev, S(stream));
+}
+
+int cleora_whiten_stats_h_dev(const uint16_t *y_h, uint64_t ldy, uint64_t n, uint32_t d, void *workspace, double *mean64_dev,
+                              double *gram_dev, void *stream) {
+    CL_REQUIRE(y_h != nullptr && workspace != nullptr && mean64_dev != nullptr && gram_dev != nullptr, "y_h / workspace / mean / gram is NULL");
+    CL_REQUIRE(gramh_applies(y_h, ldy, n, d),
+               "the f16 statistics serve d a multiple of 256 (<= 2048), n >= 4096, ldy a multiple of 8 and 16-byte aligned rows");
+    const int rc = launch_whiten_fit_stats_h(y_h, ldy, n, d, workspace, S(stream));
     if (rc != CLEORA_OK) return rc;
     return whiten_fit_copy_stats(workspace, n, d, mean64_dev, gram_dev, S(stream));
 }
@@ -973,8 +983,13 @@ namespace {
 //   The copy comes out of the f16 projection's epilogue where that form runs (d = 256, no blend); every other producer of Y — Y_0,
 //   the split projection, the blend, the stand-alone norm pass, the n = 1 row pass — is followed by one convert pass.  Statistics,
 //   the d x d step and the final whitening read the f32 Y as before.
+//   yh_only (CLEORA_F_STATS_F16; no blend, n > 1): the intermediate Y exist ONLY in yh and b2 is not used.  Statistics come from the f16
+//   matrix cores on yh (gram_h.hip) — mean and transform then belong to exactly the matrix the SpMM propagates —; the d = 256
+//   projection stores no f32 rows; every other producer writes f32 into b1 (scratch) and converts.  Where gram_h.hip does not serve
+//   the shape, or the Cholesky guard asks for exact statistics, yh is widened into b1 and the f32 statistics run on that.  The LAST
+//   projection writes the f32 Y into b1 and the final whitening is the one above.
 int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float *b2, int markov_type, uint32_t d,
-                              uint64_t iterations, float rw, uint32_t flags, float **result, uint16_t *yh = nullptr) {
+                              uint64_t iterations, float rw, uint32_t flags, float **result, uint16_t *yh = nullptr, bool yh_only = false) {
     const uint64_t n = g->n_rows;
     const uint32_t norm = (flags & CLEORA_F_L1NORM) ? CLEORA_F_L1NORM : CLEORA_F_L2NORM;
     const uint32_t fast = flags & (CLEORA_F_FASTNORM | CLEORA_F_HUB_SEGMENTS);
@@ -1017,8 +1032,14 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
     //   * the d x d step runs on the host for d <= 256, beside the SpMM.
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    const bool split_stats = any_whitening && n > 1 && gram32_applies(b1, d, n, d);
-    const bool stats_before_spmm = split_stats;
+    const bool stats16 = yh_only && yh != nullptr;
+    CL_REQUIRE(!stats16 || (!blend && n > 1), "internal: f16-only rows need a loop without a blend");
+    const bool h_stats = stats16 && any_whitening && gramh_applies(yh, d, n, d);
+    const bool split_stats = !h_stats && any_whitening && n > 1 && gram32_applies(b1, d, n, d);
+    const bool stats_before_spmm = split_stats || h_stats;
+    // gram_h.hip's Gram may be up to four times less accurate than the split form's (tests/test_gpu_stats_f16.py asserts that bound):
+    // the guard's spread cap is tightened by the same factor (eigh.hip)
+    const double spread_tighten = h_stats ? 4.0 : 1.0;
     CL_HIP(hipStreamCreateWithPriority(&st.a, hipStreamNonBlocking, prio_lo));
     CL_HIP(hipStreamCreateWithPriority(&st.b, hipStreamNonBlocking, prio_hi));
     CL_HIP(hipEventCreateWithFlags(&st.ya, hipEventDisableTiming));
@@ -1032,7 +1053,7 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
                                nullptr, nullptr, st.a)) != CLEORA_OK)
         return rc;
     if (yh && iterations > 1 && (rc = launch_convert_f32_to_f16(b1, d, n, d, yh, d, st.a)) != CLEORA_OK) return rc;
-    float *y = b1, *ynext = b2;
+    float *y = b1, *ynext = stats16 ? b1 : b2;
     const float *mean32, *transform;
     whiten_fit_result(ws.p, n, d, &mean32, &transform);
     for (uint64_t it = 0; it + 1 < iterations; ++it) {
@@ -1042,7 +1063,13 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
         // dispatcher BEFORE the SpMM's millions of small blocks: behind them they starve, the SpMM refills every hole.
         // (2) rocSOLVER synchronises with the host inside dsyevd: whatever is launched after it starts only then.
         // So: statistics (stream b) -> SpMM (stream a) -> d x d step (stream b, the host blocks here while the SpMM runs).
-        if (n > 1 && (rc = launch_whiten_fit_stats(y, d, n, d, ws.p, st.b, 1, any_whitening)) != CLEORA_OK) return rc;
+        if (h_stats) {
+            if ((rc = launch_whiten_fit_stats_h(yh, d, n, d, ws.p, st.b)) != CLEORA_OK) return rc;
+        } else {
+            // (f16-only rows outside gram_h.hip's shapes: b1 is free between two projections)
+            if (stats16 && (rc = launch_convert_f16_to_f32(yh, d, n, d, b1, d, st.b)) != CLEORA_OK) return rc;
+            if (n > 1 && (rc = launch_whiten_fit_stats(y, d, n, d, ws.p, st.b, 1, any_whitening)) != CLEORA_OK) return rc;
+        }
         if (stats_before_spmm) {                   // the SpMM only once the statistics kernels are through
             CL_HIP(hipEventRecord(st.gs, st.b));
             CL_HIP(hipStreamWaitEvent(st.a, st.gs, 0));
@@ -1056,8 +1083,11 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
         // and the PCA form follows (rare: a near-singular covariance; e.g. d > rank)
         if (n > 1) {
             bool need_exact = false;
-            if ((rc = launch_whiten_fit_solve(n, d, d, ws.p, nullptr, st.b, any_whitening, split_stats, &need_exact)) != CLEORA_OK) return rc;
+            if ((rc = launch_whiten_fit_solve(n, d, d, ws.p, nullptr, st.b, any_whitening, split_stats || h_stats, &need_exact,
+                                              spread_tighten)) != CLEORA_OK)
+                return rc;
             if (need_exact) {
+                if (h_stats && (rc = launch_convert_f16_to_f32(yh, d, n, d, b1, d, st.b)) != CLEORA_OK) return rc;
                 if ((rc = launch_whiten_fit_stats(y, d, n, d, ws.p, st.b, 1, false)) != CLEORA_OK) return rc;
                 if ((rc = launch_whiten_fit_solve(n, d, d, ws.p, nullptr, st.b, false)) != CLEORA_OK) return rc;
             }
@@ -1068,8 +1098,9 @@ int embed_whitened_overlapped(const cleora_graph *g, float *b0, float *b1, float
             // P = (alpha (Z - s mu^T) + rw (Y - mu)) T, then the row normalisation: Y of the next iteration
             bool normed = false;
             if (f16_project) {
-                rc = launch_project_f16(b0, d, n, mean32, transform, ynext, d, st.a, rowsum.as<float>(), rowabs.as<float>(),
-                                        norm == CLEORA_F_L1NORM ? 2 : 1, copy ? yh : nullptr, d);
+                // (f16-only rows: an intermediate projection stores yh alone; the last one the f32 Y of the final whitening)
+                rc = launch_project_f16(b0, d, n, mean32, transform, stats16 && copy ? nullptr : ynext, d, st.a, rowsum.as<float>(),
+                                        rowabs.as<float>(), norm == CLEORA_F_L1NORM ? 2 : 1, copy ? yh : nullptr, d);
                 normed = true;
             } else {
                 rc = launch_project(b0, d, n, d, mean32, transform, d, ynext, d, st.a, rowsum.as<float>(), blend ? y : nullptr, d,
@@ -1180,6 +1211,9 @@ static int embed_impl(const cleora_graph *g, const uint64_t *entity_hash_host, c
     CL_REQUIRE(!gather16 || (flags & CLEORA_F_WHITEN), "GATHER_F16 is for the whitened loop (CLEORA_F_WHITEN); the plain loop has ITERATE_F16");
     CL_REQUIRE(!gather16 || !(convergence_threshold > 0.0f), "GATHER_F16: the loop with a convergence threshold keeps the reference's order and gathers f32");
     CL_REQUIRE(!gather16 || (d % 4 == 0 && d <= 2048), "GATHER_F16: d must be a multiple of 4, at most 2048");
+    const bool stats16 = (flags & CLEORA_F_STATS_F16) != 0;
+    CL_REQUIRE(!stats16 || gather16, "STATS_F16 keeps the normalised rows as f16 only: it needs CLEORA_F_GATHER_F16 (and CLEORA_F_WHITEN)");
+    CL_REQUIRE(!stats16 || !(residual_weight > 0.0f), "STATS_F16: the residual blend needs the f32 normalised rows (residual_weight must be 0)");
     CL_HIP(hipSetDevice(g->device));
     auto emit = [&](const float *result, uint64_t nbytes) -> int {
         if (x_dev) {
@@ -1197,8 +1231,9 @@ static int embed_impl(const cleora_graph *g, const uint64_t *entity_hash_host, c
     DevBuf c;
     if (whitened) {
         // three buffers placed for the SpMM: it always writes `b` (mid) and reads `a` / `c` in turn
+        // (f16-only intermediate rows, STATS_F16: the SpMM's destination and ONE f32 buffer; a single entity has no statistics)
         void *bufs[3] = {nullptr, nullptr, nullptr};
-        if ((rc = alloc_iterates(g, d, 3, max_iterations, bufs, nullptr)) != CLEORA_OK) return rc;   // (the search only where the iterations can repay it)
+        if ((rc = alloc_iterates(g, d, stats16 && n > 1 ? 2 : 3, max_iterations, bufs, nullptr)) != CLEORA_OK) return rc;   // (the search only where the iterations can repay it)
         b.p = bufs[0];
         a.p = bufs[1];
         c.p = bufs[2];
@@ -1224,7 +1259,7 @@ static int embed_impl(const cleora_graph *g, const uint64_t *entity_hash_host, c
             DevBuf yh;                                     // the f16 gather copy: a plain allocation, no placement search
             if (gather16 && max_iterations > 1 && (rc = yh.alloc(bytes / 2)) != CLEORA_OK) return rc;
             rc = embed_whitened_overlapped(g, b.as<float>(), a.as<float>(), c.as<float>(), markov_type, d, max_iterations,
-                                           residual_weight, flags, &result, yh.as<uint16_t>());
+                                           residual_weight, flags, &result, yh.as<uint16_t>(), stats16 && n > 1);
             if (rc == CLEORA_OK && iterations_run) *iterations_run = max_iterations;
         } else {
             rc = embed_whitened(g, a.as<float>(), b.as<float>(), c.as<float>(), markov_type, d, max_iterations,

@@ -240,7 +240,7 @@ int cleora_embed_colsharded(cleora_colsharded *s, float *x_local, int markov_typ
     CL_REQUIRE(s != nullptr && x_local != nullptr, "handle / x is NULL");
     CL_REQUIRE(markov_type == CLEORA_LEFT || (markov_type == CLEORA_SYMMETRIC && s->has_sym), "no values for this markov_type");
     CL_REQUIRE(!(flags & CLEORA_F_ITERATE_F16), "ITERATE_F16 is served by the one-GPU plain loop only (the column partition keeps f32 slices)");
-    CL_REQUIRE(!(flags & CLEORA_F_GATHER_F16), "GATHER_F16 is served by the one-GPU whitened loop only (the column partition keeps f32 slices)");
+    CL_REQUIRE(!(flags & (CLEORA_F_GATHER_F16 | CLEORA_F_STATS_F16)), "GATHER_F16 / STATS_F16 are served by the one-GPU whitened loop only (the column partition keeps f32 slices)");
     CL_REQUIRE(!(flags & ~(CLEORA_F_FASTNORM | CLEORA_F_HUB_SEGMENTS)), "the column partition runs the plain loop (flags: HUB_SEGMENTS)");
     std::lock_guard<std::mutex> lock(s->mu);
     CL_HIP(hipSetDevice(s->device));

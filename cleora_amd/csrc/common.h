@@ -157,6 +157,10 @@ int launch_gram(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const doub
 bool gram32_applies(const float *x, uint64_t ldx, uint64_t n, uint32_t d);
 int launch_gram32(const float *x, uint64_t ldx, uint64_t n, uint32_t d, double *shift64, float *shift32, double *ws, double *gram,
                   hipStream_t stream, double *mean_out64, float *mean_out32);
+// gram_h.hip: the same statistics from f16-STORED rows (CLEORA_F_STATS_F16): uncentred sums on the f16 matrix cores, centred in f64
+bool gramh_applies(const uint16_t *y, uint64_t ldy, uint64_t n, uint32_t d);
+int launch_gram_h(const uint16_t *y, uint64_t ldy, uint64_t n, uint32_t d, double *ws, double *gram, hipStream_t stream, double *mean_out64,
+                  float *mean_out32);
 // out = (alpha * (x - rowscale (x) mean) + beta * (x2 - mean)) @ t; rowscale / x2 == nullptr: the plain (x - mean) @ t
 int launch_project(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *mean,
                    const float *t, uint32_t k, float *out, uint64_t ldo, hipStream_t stream,
@@ -171,7 +175,8 @@ int launch_project(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const f
 bool project_f16_applies(const float *x, uint64_t ldx, uint64_t n, uint32_t d, uint32_t k, const float *out, uint64_t ldo, const float *x2);
 int launch_project_f16(const float *x, uint64_t ldx, uint64_t n, const float *mean, const float *t, float *out, uint64_t ldo,
                        hipStream_t stream, const float *rowscale, const float *rowbound, int norm,
-                       uint16_t *out_h = nullptr, uint64_t ldo_h = 0);   // out_h (norm 1 / 2 only): the same rows once more, rounded to f16
+                       uint16_t *out_h = nullptr, uint64_t ldo_h = 0);   // out_h (norm 1 / 2 only): the same rows once more, rounded to f16;
+                                                                         // with out == nullptr ONLY the f16 rows are stored
 
 // similarity.hip
 uint64_t topk_workspace_bytes(uint64_t n, uint32_t k, uint32_t n_queries);
@@ -196,7 +201,8 @@ int launch_whiten_transform(const double *gram, uint64_t n, uint32_t d, uint32_t
                             double *eigenvalues, void *workspace, hipStream_t stream);
 // Cholesky form of the transform (eigh.hip): CLEORA_OK, or 1 when the covariance is not provably >= 1e-10 I (take the PCA form)
 int launch_whiten_transform_cholesky(const double *gram, uint64_t n, uint32_t d, float *transform, void *workspace,
-                                     hipStream_t stream, bool approximate_gram = false);
+                                     hipStream_t stream, bool approximate_gram = false,
+                                     double spread_tighten = 1.0);       // an approximate Gram this many times less accurate than the split-bf16 one
 uint64_t whiten_workspace(uint64_t n, uint32_t d);
 const int *whiten_info(void *workspace, uint64_t n, uint32_t d);
 const int *transform_info(void *eigh_workspace, uint32_t d);
@@ -209,12 +215,15 @@ int launch_whiten_fit(const float *x, uint64_t ldx, uint64_t n, uint32_t d, uint
                       double *eigenvalues, hipStream_t stream, int gram_blocks_per_cu = 2);
 int launch_whiten_fit_stats(const float *x, uint64_t ldx, uint64_t n, uint32_t d, void *workspace, hipStream_t stream,
                             int gram_blocks_per_cu = 2, bool intermediate = false);
+// the intermediate statistics from f16-stored rows (gramh_applies shapes only): gram_h.hip
+int launch_whiten_fit_stats_h(const uint16_t *y, uint64_t ldy, uint64_t n, uint32_t d, void *workspace, hipStream_t stream);
 // any_whitening: the caller only needs SOME W with W^T cov W = I (intermediate iterations of the L2-normalised loop):
 // Cholesky (potrf + trtri) instead of the eigensolver, falling back to it when the covariance is near-singular
 // approximate_gram: the statistics in the workspace are the split-bf16 ones; *need_exact_gram is then set (and nothing solved) when
 // the Cholesky form is refused — the caller recomputes the statistics with intermediate = false and calls again
 int launch_whiten_fit_solve(uint64_t n, uint32_t d, uint32_t k, void *workspace, double *eigenvalues, hipStream_t stream,
-                            bool any_whitening = false, bool approximate_gram = false, bool *need_exact_gram = nullptr);
+                            bool any_whitening = false, bool approximate_gram = false, bool *need_exact_gram = nullptr,
+                            double spread_tighten = 1.0);
 // ... and their location, for a projection launched separately (launch_project)
 int whiten_fit_copy_stats(void *workspace, uint64_t n, uint32_t d, double *mean64, double *gram, hipStream_t stream);
 void whiten_fit_result(void *workspace, uint64_t n, uint32_t d, const float **mean32, const float **transform);

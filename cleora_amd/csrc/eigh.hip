@@ -207,7 +207,9 @@ int launch_mean(const double *colsum, uint64_t n, uint32_t d, double *mean64, fl
 //     sum_i (trace(cov) / d) / lambda_i > kMaxRelativeSpread = 1e4: in a direction of variance lambda the
 //     transform built on that Gram is off by ~1e-7 (trace / d) / lambda, so a spread below 1e4 keeps W^T cov_exact W within
 //     1e-3 of I in the worst direction (typically two orders less: the sum runs over d terms) — and with it the clamp check
-//     holds for the exact covariance too (lambda_min >= 1e-4 trace / d >> 1e-10 + the Gram's error).
+//     holds for the exact covariance too (lambda_min >= 1e-4 trace / d >> 1e-10 + the Gram's error).  spread_tighten = f: the
+//     Gram's error is up to f times that premise (gram_h.hip's uncentred f16 sums: f = 4, the bound tests/test_gpu_stats_f16.py
+//     asserts against the split form), so the cap is 1e4 / f and the conclusion "within 1e-3 of I" is the same.
 // Two routes: d <= 256 on one host core (dxd_host.cpp: Gram down, transform up, ~1 ms — the ~215 small launches of the library
 // route cost 3.5 ms of launch latency per iteration and slow the SpMM beside them), wider matrices on rocSOLVER's potrf + trtri.
 // (A third route, a single-launch in-house kernel, measured slower than both: scripts/rejected/cholesky_whiten_kernel.hip.txt.)
@@ -227,8 +229,9 @@ __global__ __launch_bounds__(256) void diag_sum_kernel(const double *__restrict_
 }
 
 int launch_whiten_transform_cholesky(const double *gram, uint64_t n, uint32_t d, float *transform, void *workspace,
-                                     hipStream_t stream, bool approximate_gram) {
+                                     hipStream_t stream, bool approximate_gram, double spread_tighten) {
     CL_REQUIRE(gram != nullptr && transform != nullptr && workspace != nullptr, "gram / transform / workspace is NULL");
+    CL_REQUIRE(spread_tighten >= 1.0, "internal: the guard's cap is only ever tightened");
     CL_REQUIRE(n >= 2 && d > 0 && d <= (1u << 15), "bad shape");
     int device = 0;
     CL_HIP(hipGetDevice(&device));
@@ -237,7 +240,8 @@ int launch_whiten_transform_cholesky(const double *gram, uint64_t n, uint32_t d,
     const double scale = 1.0 / (double)(n - 1);
     auto trace_bound = [&](double trace_cov) {        // the largest trace(cov^-1) that passes both guards
         double bound = kMaxTraceInverse;
-        if (approximate_gram && trace_cov > 0.0 && kMaxRelativeSpread * d / trace_cov < bound) bound = kMaxRelativeSpread * d / trace_cov;
+        const double spread = kMaxRelativeSpread / spread_tighten;
+        if (approximate_gram && trace_cov > 0.0 && spread * d / trace_cov < bound) bound = spread * d / trace_cov;
         return bound;
     };
     if (d <= kHostDxdMax) {
@@ -482,15 +486,28 @@ int launch_whiten_fit_stats(const float *x, uint64_t ldx, uint64_t n, uint32_t d
     return CLEORA_OK;
 }
 
+// the statistics of f16-stored rows: no sampled shift (gram_h.hip accumulates uncentred sums); the same three timing marks
+int launch_whiten_fit_stats_h(const uint16_t *y, uint64_t ldy, uint64_t n, uint32_t d, void *workspace, hipStream_t stream) {
+    CL_REQUIRE(y != nullptr && workspace != nullptr, "y / workspace is NULL");
+    WhitenWs w;
+    whiten_ws_layout(n, d, workspace, &w);
+    wt_mark(stream);
+    wt_mark(stream);
+    const int rc = launch_gram_h(y, ldy, n, d, w.gram_ws, w.gram, stream, w.mean64, w.mean32);
+    if (rc != CLEORA_OK) return rc;
+    wt_mark(stream);
+    return CLEORA_OK;
+}
+
 int launch_whiten_fit_solve(uint64_t n, uint32_t d, uint32_t k, void *workspace, double *eigenvalues, hipStream_t stream,
-                            bool any_whitening, bool approximate_gram, bool *need_exact_gram) {
+                            bool any_whitening, bool approximate_gram, bool *need_exact_gram, double spread_tighten) {
     CL_REQUIRE(k >= 1 && k <= d && workspace != nullptr, "bad shape");
     WhitenWs w;
     whiten_ws_layout(n, d, workspace, &w);
     if (need_exact_gram) *need_exact_gram = false;
     int rc = 1;
     if (any_whitening && k == d) {            // the cheap transform where the result does not depend on which one
-        rc = launch_whiten_transform_cholesky(w.gram, n, d, w.transform, w.eigh, stream, approximate_gram);
+        rc = launch_whiten_transform_cholesky(w.gram, n, d, w.transform, w.eigh, stream, approximate_gram, spread_tighten);
         if (rc < 0) return rc;
     }
     if (rc == 1 && approximate_gram) {

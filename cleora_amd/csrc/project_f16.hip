@@ -42,7 +42,8 @@
 // COPY variant (CLEORA_F_GATHER_F16): the same kernel also stores every output row a second time, rounded to f16 (to
 // nearest even) — the operand the next SpMM gathers at half the bytes (spmm_h.hip).  Its instantiations live in a translation unit of
 // their own, project_f16_copy.hip, which includes this file with PF_COPY_TU defined and is compiled without packed f32 arithmetic;
-// this file's own object keeps the kernels, the flags and the code it had.
+// this file's own object keeps the kernels, the flags and the code it had.  COPY = 2 (CLEORA_F_STATS_F16, out == nullptr) stores ONLY
+// the f16 rows — the same values from the same registers, without the 1 KiB per row of f32 that nobody would read.
 #include <type_traits>
 
 #include "common.h"
@@ -122,7 +123,7 @@ int launch_project_f16_copy(const F16Args &a, unsigned grid, int norm, hipStream
 
 namespace {
 
-template <int NORM, bool COPY = false>
+template <int NORM, int COPY = 0>                     // COPY: 0 f32 rows, 1 f32 rows + their f16 copy, 2 the f16 rows only
 __global__ __launch_bounds__(PF_THREADS, 2) void project_f16_kernel(const F16Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *const frag = smem;                                             // [2][PF_BUF]
@@ -317,16 +318,18 @@ __global__ __launch_bounds__(PF_THREADS, 2) void project_f16_kernel(const F16Arg
                 for (int e = 0; e < 4; ++e)
                     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(o[8 * g + e]), "+v"(o[8 * g + 4 + e]));
             const uint64_t row0 = T * PF_ROWS + (uint64_t)(32 * rt + (lane & 15));
-            float *const orow = p.out + row0 * p.ldo + 32 * w + 4 * (lane >> 4);
+            if constexpr (COPY != 2) {
+                float *const orow = p.out + row0 * p.ldo + 32 * w + 4 * (lane >> 4);
 #pragma unroll
-            for (int g = 0; g < 2; ++g)
+                for (int g = 0; g < 2; ++g)
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {                                     // u: tile rows 0-15 / 16-31 of this half
-                    const float4 v = make_float4(o[8 * g + 4 * u], o[8 * g + 4 * u + 1], o[8 * g + 4 * u + 2], o[8 * g + 4 * u + 3]);
-                    if (!LAST || row0 + 16 * u < p.n)
-                        *reinterpret_cast<float4 *>(orow + (uint64_t)(16 * u) * p.ldo + 16 * g) = v;
-                }
-            if constexpr (COPY) {
+                    for (int u = 0; u < 2; ++u) {                                 // u: tile rows 0-15 / 16-31 of this half
+                        const float4 v = make_float4(o[8 * g + 4 * u], o[8 * g + 4 * u + 1], o[8 * g + 4 * u + 2], o[8 * g + 4 * u + 3]);
+                        if (!LAST || row0 + 16 * u < p.n)
+                            *reinterpret_cast<float4 *>(orow + (uint64_t)(16 * u) * p.ldo + 16 * g) = v;
+                    }
+            }
+            if constexpr (COPY != 0) {
                 // the f16 copy, from the SAME o[] the f32 stores took: each value rounded to nearest even (v_cvt_f16_f32, never the
                 // round-toward-zero pack), a lane's four columns as one 8-byte store — a 16-lane row writes 32 contiguous bytes of one
                 // matrix row, an instruction 16 rows.  (16-byte stores would take another lane exchange: DESIGN.md §2.4.)
@@ -373,7 +376,8 @@ int launch_project_f16_copy(const F16Args &a, unsigned grid, int norm, hipStream
         if (e == hipSuccess) hipLaunchKernelGGL(kernel, dim3(grid), dim3(PF_THREADS), PF_LDS, stream, a);
         return e;
     };
-    const hipError_t e = norm == 1 ? go(project_f16_kernel<1, true>) : go(project_f16_kernel<2, true>);
+    const hipError_t e = a.p.out == nullptr ? (norm == 1 ? go(project_f16_kernel<1, 2>) : go(project_f16_kernel<2, 2>))
+                                            : (norm == 1 ? go(project_f16_kernel<1, 1>) : go(project_f16_kernel<2, 1>));
     CL_HIP(e != hipSuccess ? e : hipGetLastError());
     return CLEORA_OK;
 }
@@ -392,6 +396,7 @@ int launch_project_f16(const float *x, uint64_t ldx, uint64_t n, const float *me
                        hipStream_t stream, const float *rowscale, const float *rowbound, int norm, uint16_t *out_h, uint64_t ldo_h) {
     CL_REQUIRE(project_f16_applies(x, ldx, n, PF_D, PF_D, out, ldo, nullptr), "internal: the f16 projection does not apply to this shape");
     CL_REQUIRE(mean != nullptr && t != nullptr, "mean / transform is NULL");
+    CL_REQUIRE(out != nullptr || out_h != nullptr, "out is NULL (only the projection with an f16 copy may leave the f32 rows out)");
     if (out_h) {
         CL_REQUIRE(norm == 1 || norm == 2, "the f16 copy is a copy of normalised rows: norm must be 1 or 2");
         CL_REQUIRE(ldo_h >= PF_D && ldo_h % 4 == 0 && ldo_h < (1u << 24) && (reinterpret_cast<uintptr_t>(out_h) & 7u) == 0,

@@ -641,7 +641,7 @@ int cleora_embed_sharded(cleora_sharded *s, float *x_replica, int markov_type, u
     CL_REQUIRE(d > 0, "d must be positive");
     CL_REQUIRE(markov_type == CLEORA_LEFT || (markov_type == CLEORA_SYMMETRIC && s->has_sym), "no values for this markov_type");
     CL_REQUIRE(!(flags & CLEORA_F_ITERATE_F16), "ITERATE_F16 is served by the one-GPU plain loop only (the row partition gathers f32 iterates)");
-    CL_REQUIRE(!(flags & CLEORA_F_GATHER_F16), "GATHER_F16 is served by the one-GPU whitened loop only (the row partition gathers f32 iterates)");
+    CL_REQUIRE(!(flags & (CLEORA_F_GATHER_F16 | CLEORA_F_STATS_F16)), "GATHER_F16 / STATS_F16 are served by the one-GPU whitened loop only (the row partition gathers f32 iterates)");
     std::lock_guard<std::mutex> lock(s->mu);
     CL_HIP(hipSetDevice(s->device));
     if (iterations_run) *iterations_run = 0;

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gram32_common.h"
 #include "project_common.h"
 
 namespace cleora {
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(256) void gram_mean_kernel(const double *__restrict
     for (uint32_t sl = 0; sl < s_diag; ++sl) s += colsum[(uint64_t)sl * tiles * GT + c];
     const double dl = s / (double)n;
     delta[c] = dl;
-    const double m = shift[c] + dl;
+    const double m = (shift ? shift[c] : 0.0) + dl;          // (no shift: gram_h.hip's uncentred sums)
     mean64[c] = m;
     mean32[c] = (float)m;
 }
@@ -326,8 +327,7 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double *__restri
 //     order by gram32_reduce_kernel: deterministic;
 //   * operands are centred in f32 with an f32 shift, y = x - c32 (one rounding, 3e-8 of |y|); column sums of y in f64 beside
 //     the diagonal blocks (the exact mean comes out of the same pass, as above).
-constexpr int G32_D = 256, G32_TILES = 36, G32_OFF_TILES = 64;
-
+// (the layout constants, the tile deal and the fold are in gram32_common.h: gram_h.hip's f16 kernel shares them)
 struct Gram32Args {
     const float *x;
     uint64_t ldx, n;
@@ -339,37 +339,6 @@ struct Gram32Args {
     uint32_t sub_rows;       // fold period, a multiple of the 32-row stage
     uint32_t d, S, tiles_per_slice;
 };
-
-__host__ __device__ constexpr int upper_tile_index(int tr, int tc) { return tr * 8 - tr * (tr - 1) / 2 + (tc - tr); }
-
-// The block's partial starts as zeros (written by the lanes that own the elements) so that every fold is the same
-// unconditional read-modify-write: a "first fold stores, later folds add" flag makes the compiler branch around each of the
-// loads.  The lane offset is made opaque inside the fold, or the element addresses are computed ahead of the main loop and
-// live across it in scratch; tile by tile behind sched_barrier, or all loads are batched ahead of the adds and spill.
-template <int NT, class TileIndex>
-__device__ __forceinline__ void gram32_fold(double *out, f16v (&acc)[NT], int i, int h, bool zero, TileIndex tile_index) {
-    uint32_t lo = (uint32_t)((4 * h) * 32 + i) * 8u;
-    asm volatile("" : "+v"(lo));
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-        // 32x32 C/D map: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-        char *p = reinterpret_cast<char *>(out) + tile_index(q) * 8192 + lo;
-        if (zero) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) *reinterpret_cast<double *>(p + ((reg & 3) + 8 * (reg >> 2)) * 256) = 0.0;
-        } else {
-            double old[16];
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) old[reg] = *reinterpret_cast<const double *>(p + ((reg & 3) + 8 * (reg >> 2)) * 256);
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                *reinterpret_cast<double *>(p + ((reg & 3) + 8 * (reg >> 2)) * 256) = old[reg] + (double)acc[q][reg];
-                acc[q][reg] = 0.f;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // the statistics from the bf16 matrix cores: f32-accurate Gram sums from split operands
@@ -402,16 +371,6 @@ __device__ __forceinline__ void gram32_fold(double *out, f16v (&acc)[NT], int i,
 //     accumulation is not round-to-nearest: see gram16_diag_body); f32 over <= 2048 rows, f64 across; deterministic.
 constexpr int G16_KR = 32;                    // rows per stage
 constexpr int G16_THREADS = 512;
-constexpr int G16_TR[8][5] = {{0, 0, 0, 0, -1}, {0, 0, 0, 0, -1}, {1, 1, 1, 1, -1}, {1, 1, 1, 7, -1},
-                              {2, 2, 2, 2, 2},  {2, 3, 3, 3, 3},  {3, 4, 4, 4, 4},  {5, 5, 5, 6, 6}};
-constexpr int G16_TC[8][5] = {{0, 1, 2, 3, -1}, {4, 5, 6, 7, -1}, {1, 2, 3, 4, -1}, {5, 6, 7, 7, -1},
-                              {2, 3, 4, 5, 6},  {7, 3, 4, 5, 6},  {7, 4, 5, 6, 7},  {5, 6, 7, 6, 7}};
-__host__ __device__ constexpr int g16_ntiles(int w) { return w < 4 ? 4 : 5; }
-__host__ __device__ constexpr bool g16_uses(int w, int blk) {
-    for (int q = 0; q < g16_ntiles(w); ++q)
-        if (G16_TR[w][q] == blk || G16_TC[w][q] == blk) return true;
-    return false;
-}
 // byte offset of a fragment piece inside a stage: NS split pieces x NCB column blocks per k-step
 template <int NS, int NCB>
 __device__ __forceinline__ uint32_t g16_slot(int ks, int s, int cbk, int lane) { return (uint32_t)((((ks * NS + s) * NCB + cbk) * 64 + lane) * 16); }
@@ -459,7 +418,6 @@ __device__ __forceinline__ float g16_stage_task(const float (&pre)[8], int nv, f
 }
 
 #define G16_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0)
-constexpr f16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 // the products of one (tile, k-step): operand pieces (A, B); the first starts from zero at ks == 0
 constexpr int G16_PA[6] = {0, 0, 1, 1, 0, 2}, G16_PB[6] = {0, 1, 0, 1, 2, 0};
 constexpr int G16_LA[3] = {0, 0, 1}, G16_LB[3] = {0, 1, 0};
@@ -1324,8 +1282,7 @@ __global__ __launch_bounds__(RG * 128, RG == 2 ? 2 : 1) void project_split_kerne
 }  // namespace
 
 constexpr uint64_t kLeanGramMinRows = 1ull << 20;
-struct Gram32Plan { uint32_t S, blocks, tiles_per_slice, slices; };
-inline Gram32Plan gram32_plan(uint64_t n, uint32_t d) {
+Gram32Plan gram32_plan(uint64_t n, uint32_t d) {
     Gram32Plan p;
     p.S = d / G32_D;
     p.blocks = p.S + p.S * (p.S - 1);
@@ -1375,7 +1332,6 @@ int launch_gram32(const float *x, uint64_t ldx, uint64_t n, uint32_t d, double *
     a.partial = ws;
     a.colsum = ws + (uint64_t)q.slices * q.tiles_per_slice * 1024;
     a.diagfix = a.colsum + (uint64_t)q.slices * d;
-    double *delta = a.diagfix + (uint64_t)q.slices * d;
     uint64_t rps = (n + q.slices - 1) / q.slices;
     a.rows_per_slice = (rps + G16_KR - 1) / G16_KR * G16_KR;           // whole stages
     a.sub_rows = 2048;
@@ -1391,10 +1347,16 @@ int launch_gram32(const float *x, uint64_t ldx, uint64_t n, uint32_t d, double *
     const size_t ncb = q.S == 1 ? 8 : 12;
     if (six) CL_HIP(go(gram16_kernel<false>, 2 * 2 * 3 * ncb * 1024));
     else CL_HIP(go(gram16_kernel<true>, 2 * 2 * 2 * ncb * 1024));
-    hipLaunchKernelGGL(gram_mean_kernel, dim3((d + 255) / 256), dim3(256), 0, stream, a.colsum, q.slices, d / GT, d, n, shift64, delta,
+    return launch_gram32_finish(ws, q.slices, q, n, d, shift64, !six, gram, mean_out64, mean_out32, stream);
+}
+
+int launch_gram32_finish(double *ws, uint32_t slices, const Gram32Plan &q, uint64_t n, uint32_t d, const double *shift64, bool diagfix,
+                         double *gram, double *mean_out64, float *mean_out32, hipStream_t stream) {
+    double *colsum = ws + (uint64_t)slices * q.tiles_per_slice * 1024, *fix = colsum + (uint64_t)slices * d, *delta = fix + (uint64_t)slices * d;
+    hipLaunchKernelGGL(gram_mean_kernel, dim3((d + 255) / 256), dim3(256), 0, stream, colsum, slices, d / GT, d, n, shift64, delta,
                        mean_out64, mean_out32);
-    hipLaunchKernelGGL(gram32_reduce_kernel, dim3(4, q.tiles_per_slice), dim3(256), 0, stream, ws, q.slices, q.S, q.tiles_per_slice, d,
-                       delta, (double)n, six ? nullptr : a.diagfix, gram);
+    hipLaunchKernelGGL(gram32_reduce_kernel, dim3(4, q.tiles_per_slice), dim3(256), 0, stream, ws, slices, q.S, q.tiles_per_slice, d,
+                       delta, (double)n, diagfix ? fix : nullptr, gram);
     CL_HIP(hipGetLastError());
     return CLEORA_OK;
 }

@@ -156,6 +156,8 @@ def embed(graph, feature_dim=DEFAULT_FEATURE_DIM, num_iterations=DEFAULT_NUM_ITE
             # install(gather_dtype="f16"): a preference — only the reorganised loop (no threshold) at the widths the f16 gather serves
             if _pyc.gather_f16() and not convergence_threshold > 0 and d % 4 == 0 and d <= 2048:
                 flags |= _hip.F_GATHER_F16
+                if _pyc.stats_f16() and not residual_weight > 0:   # install(stats_dtype="f16"): the f16 rows alone, where nothing blends them
+                    flags |= _hip.F_STATS_F16
             _hip.check(L.cleora_embed(graph._graph().handle, _hip.ptr(hashes), _hip.ptr(x0), kind, d, int(num_iterations), int(seed),
                                       float(residual_weight), float(max(convergence_threshold, 0.0)), flags,
                                       _hip.ptr(out), ctypes.byref(ran)))

@@ -81,6 +81,23 @@ def gather_f16():
     return _GATHER_F16
 
 
+_STATS_F16 = False      # set by cleora_amd.install(stats_dtype=...)
+
+
+def set_stats_dtype(dtype):
+    """Where the whitened one-call loop keeps its intermediate normalised rows when it gathers f16 (set_gather_dtype): "f32" (default: an
+    f32 matrix for the statistics beside the f16 copy) or "f16" (CLEORA_F_STATS_F16: the f16 rows alone, statistics from the f16 matrix
+    cores).  A preference: it applies to the calls the f16 gather applies to, and only with residual_weight == 0."""
+    global _STATS_F16
+    if dtype not in ("f16", "f32"):
+        raise ValueError(f"stats_dtype must be 'f16' or 'f32', got {dtype!r}")
+    _STATS_F16 = dtype == "f16"
+
+
+def stats_f16():
+    return _STATS_F16
+
+
 def loop_flags():
     on = _HUB_SEGMENTS if _HUB_SEGMENTS is not None else os.environ.get("CLEORA_HUB_SEGMENTS", "").strip() not in ("", "0")
     return _hip.F_HUB_SEGMENTS if on else 0

@@ -80,6 +80,10 @@ extern "C" {
 #define CLEORA_F_GATHER_F16 8192u  /* cleora_embed / cleora_embed_dev with CLEORA_F_WHITEN and no convergence threshold: every SpMM after
                                     * the first GATHERS an f16 copy of the normalised rows (cleora_propagate_hf_dev); sums, statistics
                                     * and projections stay f32.  Opt-in and not the reference's bits; see cleora_embed */
+#define CLEORA_F_STATS_F16 16384u  /* only together with CLEORA_F_GATHER_F16, residual_weight == 0: the intermediate normalised rows exist
+                                    * ONLY as f16 — statistics from the f16 matrix cores on the stored values
+                                    * (cleora_whiten_stats_h_dev), the d = 256 projection stores no f32 rows, two iterate buffers
+                                    * plus the f16 one instead of three.  Opt-in; see cleora_embed */
 
 typedef struct cleora_graph cleora_graph; /* device-resident CSR shard (struct SparseMatrix, src/sparse_matrix.rs:56-78) */
 
@@ -329,7 +333,9 @@ int cleora_project_bounded_dev(const float *x, uint64_t ldx, uint64_t n, uint32_
 /* cleora_project_bounded_dev where its f16 form applies (d = k = 256, 16-byte-aligned rows: CLEORA_E_INVALID elsewhere) and norm
  * is 1 or 2, with a SECOND output: out_h[r][j] = the f16 nearest (ties to even) to the out[r][j] the call stores, ldo_h halfs per row
  * (ldo_h % 4 == 0, out_h 8-byte aligned), written by the same kernel's epilogue.  out is bit-identical to
- * cleora_project_bounded_dev's.  The operand of cleora_propagate_hf_dev in the next iteration of the whitened loop. */
+ * cleora_project_bounded_dev's.  The operand of cleora_propagate_hf_dev in the next iteration of the whitened loop.
+ * out == NULL (ldo is then ignored): only out_h is stored — the same bits — and the 4 d bytes per row of f32 are never written
+ * (CLEORA_F_STATS_F16: nobody reads them). */
 int cleora_project_bounded_h_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *mean_f32_dev,
                                  const float *transform_dev, uint32_t k, float *out, uint64_t ldo, const float *rowscale_dev,
                                  const float *rowbound_dev, int norm, int *norm_done, int *form, uint16_t *out_h, uint64_t ldo_h,
@@ -363,6 +369,16 @@ int cleora_whiten_transform_dev(const double *gram_dev, uint64_t n, uint32_t d, 
  * workspace: cleora_whiten_workspace(n, d) BYTES; mean64_dev: f64[d]; gram_dev: f64[d*d].  n >= 2. */
 int cleora_whiten_stats_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, void *workspace, int intermediate,
                             double *mean64_dev, double *gram_dev, void *stream);
+
+/* The same two outputs for rows STORED as IEEE binary16 (csrc/gram_h.hip; what the whitened loop runs under CLEORA_F_STATS_F16): the
+ * exact f64 mean of the f16 values and sum_r (y_r - mean)(y_r - mean)^T in f64.  One MFMA (v_mfma_f32_32x32x16_f16) per tile and
+ * k-step on the values as stored — a product of two f16 values is exact in f32 — accumulating the UNCENTRED sums (32 rows on the
+ * matrix cores, f32 over <= 2048 rows, f64 across; deterministic) and centring in f64 at the end.  An intermediate-iteration form like
+ * intermediate = 1 above: its error is that form's times a small factor (the sums are rounded relative to the uncentred entries).
+ * Shapes: d a multiple of 256 (<= 2048), n >= 4096, ldy (in f16 elements) a multiple of 8, y_h 16-byte aligned; CLEORA_E_INVALID
+ * elsewhere.  workspace: cleora_whiten_workspace(n, d) BYTES. */
+int cleora_whiten_stats_h_dev(const uint16_t *y_h, uint64_t ldy, uint64_t n, uint32_t d, void *workspace, double *mean64_dev,
+                              double *gram_dev, void *stream);
 
 /* The transform for the INTERMEDIATE iterations of the loop E <- whiten(l2_normalise(A E)) (pycleora/__init__.py:109-117):
  * inside that loop any W with W^T cov W = I gives the same final embedding as the reference's PCA form (two whitenings

@@ -10,12 +10,20 @@ third launch), interleaves
 every launch between two HIP events on the launch stream; then (3) `--loops` pairs of an `--iterations`-iteration whitened
 cleora_embed_dev without and with the flag (the library's own loop timer: the loop runs on streams of its own).  Medians and ranges;
 the SpMMs' bytes/s on their own gather models as fractions of the 8 TB/s peak.  --resources / --loop-test: the compiler's register
-report for the d = 256 and d = 1024 kernels and the d = 256 figures printed by tests/test_gpu_gather_f16.py, copied into the record."""
+report for the d = 256 and d = 1024 kernels and the d = 256 figures printed by tests/test_gpu_gather_f16.py, copied into the record.
+
+--stats-f16 (CLEORA_F_STATS_F16; write it to profiles/stats_f16_c3.json) adds, in the same process: (4) the statistics stage —
+cleora_whiten_stats_dev(intermediate = 1) on the f32 rows against cleora_whiten_stats_h_dev on their f16 copy — with both Grams' errors
+against an f64 Gram of the f16 values (torch, f64, on the device); the projection that stores only the f16 rows in (2); the loop with
+GATHER_F16 | STATS_F16 as a third member of (3), and every loop's peak device memory (the driver's free memory sampled from a thread
+while the call runs, against the free memory before it)."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import threading
+import time
 import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,6 +44,7 @@ LOOP_TEST_D256 = {  # tests/test_gpu_gather_f16.py, (6000, 256, 4, symmetric): l
     "rw=0": {"delta_models": 1.53e-4, "gpu_f32_gather": 4.03e-7, "gpu_f16_gather": 1.42e-4},
     "rw=0.3": {"delta_models": 7.32e-5, "gpu_f32_gather": 1.45e-7, "gpu_f16_gather": 8.06e-5},
 }
+STATS_F16_TEST = {"statistics_e_new_e_old": {"n=4096 d=256": [4.44e-08, 2.57e-08], "n=4096 d=512": [6.03e-08, 3.4e-08], "n=4099 d=256": [4.46e-08, 2.47e-08], "n=4099 d=512": [6e-08, 3.45e-08], "n=6151 d=256": [3.66e-08, 2.2e-08], "n=6151 d=512": [4.99e-08, 2.92e-08], "n=4096 d=256 with 2048-row folds (rejected)": [2.8e-07, 2.57e-08]}, "loop_delta_models_gpu_f16_only_gpu_f16_gather": {"6000x256, 4 it.": [0.000132, 0.000146, 0.000142], "5000x512, 3 it.": [8.96e-05, 7.79e-05, 9.04e-05], "20000x64, 6 it.": [0.000387, 0.000366, 0.000399]}, "gramh_kernel_vgpr_scratch_waves_lds": [225, 0, 2, "64 KiB (d = 256) / 96 KiB"]}  # tests/test_gpu_stats_f16.py as printed on an MI355X, and hipcc's report for gramh_kernel
 
 
 def summary(ms):
@@ -55,8 +64,56 @@ def interleave(runs, launches):
     return times
 
 
+def gram_errors(L, y32, y16, n, d):
+    """||G - G64||_F / ||G64||_F of both intermediate forms on the same (f16-representable) values, and their times"""
+    dev = y32.device
+    y32.copy_(y16)                                                    # the widened rows: both forms see the same values
+    mean = torch.zeros(d, dtype=torch.float64, device=dev)
+    gram = torch.zeros((d, d), dtype=torch.float64, device=dev)
+    step = 1 << 19
+    for r in range(0, n, step):
+        mean += y16[r:r + step].double().sum(dim=0)
+    mean /= n
+    for r in range(0, n, step):
+        c = y16[r:r + step].double() - mean
+        gram += c.T @ c
+    ws = torch.empty(L.cleora_whiten_workspace(n, d), dtype=torch.uint8, device=dev)
+    m, g = torch.empty(d, dtype=torch.float64, device=dev), torch.empty((d, d), dtype=torch.float64, device=dev)
+    runs = (("split_bf16_on_f32_rows", lambda: _hip.check(L.cleora_whiten_stats_dev(y32.data_ptr(), d, n, d, ws.data_ptr(), 1, m.data_ptr(), g.data_ptr(), None))),
+            ("f16_mfma_on_f16_rows", lambda: _hip.check(L.cleora_whiten_stats_h_dev(y16.data_ptr(), d, n, d, ws.data_ptr(), m.data_ptr(), g.data_ptr(), None))))
+    out = {}
+    for name, run in runs:
+        run()
+        torch.cuda.synchronize()
+        out[name] = {"gram_rel_frobenius_error": float((g - gram).norm() / gram.norm()), "mean_max_abs_error": float((m - mean).abs().max())}
+    for name, ms in interleave(runs, 20).items():
+        out[name].update(summary(ms))
+    out["mean_norm_squared"] = float((mean * mean).sum())
+    return out
+
+
+def peak_memory_during(call):
+    """bytes of device memory taken while call() runs: the largest drop of the driver's free memory, sampled every 2 ms"""
+    free0 = torch.cuda.mem_get_info()[0]
+    low, done = [free0], threading.Event()
+
+    def sample():
+        while not done.is_set():
+            low[0] = min(low[0], torch.cuda.mem_get_info()[0])
+            time.sleep(0.002)
+    th = threading.Thread(target=sample)
+    th.start()
+    try:
+        call()
+    finally:
+        done.set()
+        th.join()
+    return free0 - low[0]
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stats-f16", action="store_true")
     ap.add_argument("--config", default="C3", choices=sorted(bench.CONFIGS))
     ap.add_argument("--nodes", type=int, default=0)
     ap.add_argument("--pairs", type=int, default=0)
@@ -105,6 +162,10 @@ def main():
     torch.cuda.synchronize()
     rec["spmm"]["max_abs_diff_of_the_outputs"] = float((zf - z32).abs().max())     # z32: from the f32 gather; zf: from the f16 gather
     del zf
+    if args.stats_f16:
+        rec["stats_f16_test"] = STATS_F16_TEST
+    if args.stats_f16 and d % 256 == 0:
+        rec["statistics"] = gram_errors(L, y32, y16, n, d)
 
     if d == 256:
         # the projection of an intermediate iteration: x = Z (bounded row by row), a centring vector and a transform of whitening size
@@ -127,25 +188,41 @@ def main():
         def convert():
             _hip.check(L.cleora_convert_f32_to_f16_dev(out.data_ptr(), d, n, d, y16.data_ptr(), d, None))
 
+        def project_f16_only():
+            _hip.check(L.cleora_project_bounded_h_dev(z32.data_ptr(), d, n, d, mean.data_ptr(), t.data_ptr(), d, None, d, rowsum.data_ptr(),
+                                                      rowabs.data_ptr(), 1, None, None, y16.data_ptr(), d, None))
+
+        forms = (("no_copy", project), ("with_copy_8_byte_stores", project_copy), ("separate_convert_pass", convert))
+        if args.stats_f16:
+            forms += (("f16_rows_only", project_f16_only),)
         for _ in range(2):
-            project()
-            project_copy()
-            convert()
+            for _, run in forms:
+                run()
         torch.cuda.synchronize()
-        times = interleave((("no_copy", project), ("with_copy_8_byte_stores", project_copy), ("separate_convert_pass", convert)), args.launches)
+        times = interleave(forms, args.launches)
         rec["projection"] = {name: summary(ms) for name, ms in times.items()}
         del out, rowsum, rowabs
     del y32, y16
 
     # the whitened loop, device-resident, without and with the flag (pairs interleaved; the library's loop timer)
-    loop = {"f32": [], "f16": []}
+    variants = (("f32", 0), ("f16", _hip.F_GATHER_F16))
+    if args.stats_f16:
+        variants += (("f16_rows_only", _hip.F_GATHER_F16 | _hip.F_STATS_F16),)
+    loop, peak = {name: [] for name, _ in variants}, {name: 0 for name, _ in variants}
     for _ in range(args.loops):
-        for name, flag in (("f32", 0), ("f16", _hip.F_GATHER_F16)):
+        for name, flag in variants:
             _hip.check(L.cleora_init_dev(hashes.data_ptr(), n, d, 0, z32.data_ptr(), d, None))
             torch.cuda.synchronize()
-            _hip.check(L.cleora_embed_dev(graph.handle, z32.data_ptr(), _hip.LEFT, d, args.iterations, 0.0, 0.0, _hip.F_WHITEN | flag, None))
+            run = lambda: _hip.check(L.cleora_embed_dev(graph.handle, z32.data_ptr(), _hip.LEFT, d, args.iterations, 0.0, 0.0, _hip.F_WHITEN | flag, None))
+            if args.stats_f16:
+                peak[name] = max(peak[name], peak_memory_during(run))
+            else:
+                run()
             loop[name].append(float(L.cleora_last_embed_loop_ms()))
     rec["whitened_loop"] = {"iterations": args.iterations, "pairs": args.loops, **{name: summary(ms) for name, ms in loop.items()}}
+    if args.stats_f16:
+        rec["whitened_loop"]["peak_device_bytes_inside_the_call"] = peak
+        rec["whitened_loop"]["iterate_bytes"] = n * d * 4
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(rec, f, indent=1)

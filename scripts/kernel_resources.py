@@ -8,11 +8,11 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "cleora_amd", "csrc")
 lines = ["# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage over cleora_amd/csrc/*.hip "
          "(build flags of build.sh): file, kernel, VGPRs, AGPRs, scratch bytes/lane, waves/SIMD, LDS bytes/block"]
-for f in ("spmm", "spmm_h", "rowops", "whiten", "project_f16", "project_f16_copy", "eigh", "hot", "attention", "similarity", "abi", "peer", "sharded", "colsharded", "multi", "stager"):
+for f in ("spmm", "spmm_h", "rowops", "whiten", "gram_h", "project_f16", "project_f16_copy", "eigh", "hot", "attention", "similarity", "abi", "peer", "sharded", "colsharded", "multi", "stager"):
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]
-    if f == "whiten":
+    if f in ("whiten", "gram_h"):
         cmd += ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-    if f in ("spmm_h", "project_f16_copy"):
+    if f in ("spmm_h", "gram_h", "project_f16_copy"):
         cmd += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     cmd += ["-c", f + ".hip", "-o", "/tmp/kernel_resources.o", "-Rpass-analysis=kernel-resource-usage"]
     log = subprocess.run(cmd, cwd=src, capture_output=True, text=True).stderr
