@@ -170,6 +170,8 @@ SIGNATURES = {
     "cleora_topk_set_route": (c_int, [c_int]),
     "cleora_cholesky_whiten_host": (c_int, [vp, c_u64, c_u32, vp, vp]),
     "cleora_topk_cosine_dev": (c_int, [vp, vp, c_u64, c_u64, c_u32, vp, c_u32, c_u32, c_int, c_int, vp, vp, vp, vp]),
+    "cleora_knn_workspace": (c_u64, [c_u64, c_u32, c_u32, c_u64]),
+    "cleora_knn_cosine_dev": (c_int, [vp, vp, c_u64, c_u64, c_u32, vp, c_u64, c_u32, c_int, c_int, vp, vp, vp, vp]),
     "cleora_propagate": (c_int, [vp, c_int, vp, c_u32, vp]),
     "cleora_l2_normalize": (c_int, [vp, c_u64, c_u32, vp]),
     "cleora_init": (c_int, [vp, c_u64, c_u32, c_i64, vp]),

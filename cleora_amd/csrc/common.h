@@ -184,6 +184,12 @@ int launch_topk_cosine(const cleora_graph *g, const float *x, uint64_t ldx, uint
                        const uint32_t *queries_dev, uint32_t n_queries, uint32_t k, int exclude_self, int exclude_edges,
                        uint32_t *out_index, float *out_score, void *workspace, hipStream_t stream);
 
+// knn.hip: the fused form for many queries — scores on the matrix cores, selection in the kernel, no n x n_queries scores
+uint64_t knn_workspace_bytes(uint64_t n, uint32_t d, uint32_t k, uint64_t n_queries);
+int launch_knn_cosine(const cleora_graph *g, const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint32_t *queries_dev,
+                      uint64_t n_queries, uint32_t k, int exclude_self, int exclude_edges, uint32_t *out_index, float *out_score,
+                      void *workspace, hipStream_t stream);
+
 // stager.hip: pageable host memory <-> device through a pinned ring, at PCIe speed
 int staged_h2d(void *dst_dev, const void *src_host, uint64_t bytes, hipStream_t after);
 int staged_d2h(void *dst_host, const void *src_dev, uint64_t bytes, hipStream_t after);

@@ -291,3 +291,29 @@ def find_most_similar(graph, embeddings, query_entity, top_k=10, exclude_self=Tr
     # with -2: report -1 for it like the reference
     return [{"entity_id": ids[int(i)], "index": int(i), "similarity": float(-1.0 if (exclude_self and int(i) == query_idx) else v)}
             for i, v in zip(idx, sims)][:k]
+
+
+def nearest_neighbours(embeddings, k=10, queries=None, graph=None, exclude_self=True, exclude_existing=False):
+    """The kNN graph of an embedding: (index uint32[nq, k], score float32[nq, k]), the k most cosine-similar rows of every
+    query row in descending score (ties: the larger row index first).  queries: row indices (any order, repeats allowed) or
+    None for every row.  exclude_self masks the query itself, exclude_existing (needs `graph`, the square graph of the rows)
+    every stored edge in either direction; masked rows score -2 and only appear when fewer than k others exist.
+    One upload, one call of the fused kernel (cleora_knn_cosine_dev: no n x nq score matrix), one download of nq * k pairs;
+    k beyond CLEORA_KNN_MAX_K or a row wider than the kernel takes goes through the batched top-k path."""
+    from . import variants as _var
+    x = np.ascontiguousarray(embeddings, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("embeddings must be a 2-D array")
+    n, d = x.shape
+    if exclude_existing and graph is None:
+        raise ValueError("exclude_existing=True needs the graph")
+    rows = None if queries is None else np.asarray(queries, dtype=np.int64).ravel()
+    if rows is not None and rows.size and (rows.min() < 0 or rows.max() >= n):
+        raise ValueError("query row index out of range")
+    k = min(int(k), n)
+    nq = n if rows is None else rows.size
+    if k <= 0 or nq == 0 or d == 0:
+        return np.empty((nq, max(k, 0)), np.uint32), np.empty((nq, max(k, 0)), np.float32)
+    if k > _var.KNN_MAX_K or d > _var.KNN_MAX_D:
+        return _var._topk_neighbours(graph, x, np.arange(n) if rows is None else rows, k, bool(exclude_self), bool(exclude_existing))
+    return _var._knn_fused(graph, x, rows, k, bool(exclude_self), bool(exclude_existing))

@@ -12,6 +12,7 @@ order) — a relative difference of ~1e-6 per iteration, which the parity tests 
     embed_directed        (:362-410)    embed_with_attention  (:206-276)
     embed_edge_features   (:784-852)    predict_links         (:636-681)
 """
+import contextlib
 from itertools import combinations
 
 import numpy as np
@@ -211,6 +212,31 @@ def predict_links(graph, embeddings, top_k=10, exclude_existing=True, source_ent
 TOPK_DEVICE_MAX = 1024      # cleora_topk_cosine_dev selects at most this many per query (csrc/similarity.hip)
 
 
+KNN_MAX_K = 32              # CLEORA_KNN_MAX_K: what the fused kernel (csrc/knn.hip) selects per query
+KNN_MAX_D = 16384           # ... and the widest row it takes
+# From this many queries on _topk_neighbours takes the fused kernel.  Measured (scripts/knn_probe.py --part threshold; MI355X,
+# n = 262 144, d = 256, k = 10; batched ms / fused ms): 64 queries 0.55 / 0.98, 256: 0.65 / 0.99, 1024: 2.31 / 2.93,
+# 4096: 9.00 / 8.22 (x1.10 rounded, 9.5 %), 16384: 35.8 / 27.6 (x1.30) — the smallest of these with at least 10 %.
+KNN_FUSED_MIN_QUERIES = 16384
+
+
+def _knn_fused(graph, x, query_rows, k, exclude_self, exclude_existing):
+    """cleora_knn_cosine_dev: one upload of x, one call, one download of the nq x k pairs.  query_rows None = every row."""
+    L = _hip.lib()
+    n, d = x.shape
+    nq = n if query_rows is None else len(query_rows)
+    dx = _hip.DevArray.from_host(x)
+    dq = None if query_rows is None else _hip.DevArray.from_host(np.asarray(query_rows, dtype=np.uint32))
+    oi, os_ = _hip.DevArray((nq, k), np.uint32), _hip.DevArray((nq, k), np.float32)
+    ws = _hip.DevArray((L.cleora_knn_workspace(n, d, k, nq),), np.uint8)
+    with graph._lock if exclude_existing else contextlib.nullcontext():
+        g = graph._graph().handle if exclude_existing else None
+        _hip.check(L.cleora_knn_cosine_dev(g, dx.ptr, d, n, d, None if dq is None else dq.ptr, nq, k, 1 if exclude_self else 0,
+                                           1 if exclude_existing else 0, oi.ptr, os_.ptr, ws.ptr, None))
+        _hip.check(L.cleora_stream_sync(None))
+    return oi.to_host(), os_.to_host()
+
+
 def _topk_by_host_selection(graph, x, query_rows, k, exclude_self, exclude_existing, self_score=-2.0):
     """The same result for k > TOPK_DEVICE_MAX (the reference accepts any top_k): the scores still come from the device
     (cleora_cosine_scores_dev, one pass over X per query), the masks and the selection run on the host like the
@@ -250,11 +276,13 @@ def _topk_neighbours(graph, x, query_rows, k, exclude_self, exclude_existing):
     L = _hip.lib()
     n, d = x.shape
     nq = len(query_rows)
+    if nq >= KNN_FUSED_MIN_QUERIES and k <= KNN_MAX_K and d <= KNN_MAX_D:
+        return _knn_fused(graph, x, query_rows, k, exclude_self, exclude_existing)
     dx = _hip.DevArray.from_host(x)
     dq = _hip.DevArray.from_host(np.asarray(query_rows, dtype=np.uint32))
     oi, os_ = _hip.DevArray((nq, k), np.uint32), _hip.DevArray((nq, k), np.float32)
     ws = _hip.DevArray((L.cleora_topk_workspace_for(n, k, nq),), np.uint8)
-    with graph._lock:
+    with graph._lock if graph is not None else contextlib.nullcontext():
         g = graph._graph().handle if exclude_existing else None
         _hip.check(L.cleora_topk_cosine_dev(g, dx.ptr, d, n, d, dq.ptr, nq, k, 1 if exclude_self else 0,
                                             1 if exclude_existing else 0, oi.ptr, os_.ptr, ws.ptr, None))

@@ -643,6 +643,27 @@ int cleora_topk_cosine_dev(const cleora_graph *g, const float *x, uint64_t ldx, 
 int cleora_topk_last_route(void);
 int cleora_topk_set_route(int route);
 
+/* The same neighbours for MANY queries at once — the kNN graph of an embedding — by one fused kernel (csrc/knn.hip): a block
+ * keeps 64 normalised query rows in LDS, streams the rows of X past them in tiles of 128 on the f32 matrix cores and selects
+ * inside the kernel (a threshold per query, survivors into an LDS buffer, the k best kept under the order below).  No score
+ * matrix exists: nothing proportional to n_queries x n is stored, the CSR is read only for scores that survive the threshold.
+ *   Scores, exclude_self, exclude_existing, output layout ([n_queries][k], descending; ties: the larger row index first; masked
+ *   entries come out with -2 only when fewer than k unmasked rows exist): exactly as cleora_topk_cosine_dev above.  The columns
+ *   of a CSR row may be in any order.  Same input, same output bits.
+ *   query_rows_dev: n_queries row indices < n, in any order, repeats allowed; NULL = the rows 0 .. n_queries - 1.
+ *   Limits: 1 <= k <= min(n, CLEORA_KNN_MAX_K), n < 2^32, 1 <= d <= 16384, ldx >= d, n_queries < 2^29; anything else returns
+ *   CLEORA_E_INVALID (use cleora_topk_cosine_dev for a larger k).  d <= 256: the query tile is resident; wider rows re-stage it
+ *   in 32-column chunks next to X.  Few queries against many rows: the rows are split over up to 64 blocks per query tile and a
+ *   small second kernel merges their lists.
+ *   workspace: cleora_knn_workspace(n, d, k, n_queries) BYTES — 1 / ||x_r|| (n floats), the packed normalised queries
+ *   (n_queries x d floats, both rounded up to the tile), the split lists; monotone in every argument, plain host arithmetic.
+ * Only enqueues on `stream`: never waits for it and copies nothing to the host; arguments are checked before any device work. */
+#define CLEORA_KNN_MAX_K 32
+uint64_t cleora_knn_workspace(uint64_t n, uint32_t d, uint32_t k, uint64_t n_queries);
+int cleora_knn_cosine_dev(const cleora_graph *g, const float *x, uint64_t ldx, uint64_t n, uint32_t d,
+                          const uint32_t *query_rows_dev, uint64_t n_queries, uint32_t k, int exclude_self,
+                          int exclude_existing, uint32_t *out_index_dev, float *out_score_dev, void *workspace, void *stream);
+
 /* ---- host-pointer entry points: what the PyO3 methods call ------------------------- */
 
 /* SparseMatrix::markov_propagate → NdArrayMatrix::multiply (src/lib.rs:29-47, src/embedding.rs:15-39).
