@@ -3,32 +3,23 @@
 // Replaces NdArrayMatrix::spmm_kernel / multiply_into / l2_normalize_inplace and the
 // per-iteration body of embed_full (src/embedding.rs:41-136).
 //
-// Mapping to the hardware:
-//   * one GROUP of G lanes owns one output row; G = 64 (a whole wavefront) for d >= 256, so
-//     one gathered embedding row is ONE coalesced `global_load_dwordx4` per 1 KiB (lane l
-//     reads bytes [16 l, 16 l + 16) of the row); narrower d packs 64/G rows per wavefront.
-//   * the row's (col, val) slice is fetched 64 (G) entries at a time with one coalesced load
-//     into registers and broadcast edge by edge with v_readlane (G = 64: the column index
-//     lands in an SGPR, so the gather address is scalar-base + lane offset) or ds_bpermute.
-//   * U*V >= 8 independent 16-byte loads are in flight per lane before the first use; with 8
-//     waves per SIMD that is >= 256 KiB of gathers in flight per CU.
-//   * edges are consumed in stored order with separate f32 multiply and add
-//     (-ffp-contract=off + __fmul_rn/__fadd_rn), so every row that is not split is
-//     bit-identical to the reference's sequential accumulate (src/embedding.rs:80-82).
-//   * rows longer than hub_threshold (hub rows) are summed IN THE REFERENCE'S ORDER too, by
+// The row kernel's schedule of work items, edge loop and hot / cold gather are spmm_rows.h, shared with
+// spmm_h.hip.  This file adds:
+//   * the f32 source policy: U*V >= 8 independent 16-byte loads in flight per lane before the first use; a scalar (W = 1) path
+//     for unaligned rows;
+//   * rows longer than hub_threshold (hub rows) summed IN THE REFERENCE'S ORDER, by
 //     hub_inorder_kernel on a side stream beside the main launch: one wavefront per (hub row,
 //     64-column slab), four edges per 16-byte load instruction (a lane quad per edge), 48 loads =
 //     192 edges in flight per wavefront, the running sum handed from quad to quad with a DPP row
 //     rotate so that every output element sees `acc += w * x` edge by edge, like
 //     src/embedding.rs:76-83.  hub_epilogue_kernel then runs the row epilogue on the whole row.
-//   * with CLEORA_F_HUB_SEGMENTS the hub rows are instead cut into hub_segment-edge segments that
-//     are the FIRST work items of the main launch, each on its own wavefront, and combined in a
-//     fixed order by hub_finish_kernel: deterministic and immune to a pathological hub (a chain
-//     of 10^8 dependent adds), but not the reference's summation order.
+//     The rows between hub_threshold and the hub launch's minimum are the FIRST work items of the main launch (mid rows);
+//   * with CLEORA_F_HUB_SEGMENTS the segmented schedule of spmm_rows.h instead, finished by hub_finish_kernel;
 //   * the epilogue (residual blend, L2 normalise, squared difference) runs on the
 //     accumulator registers, so Y is written exactly once and never re-read.
 #include "common.h"
 #include "row_epilogue.h"
+#include "spmm_rows.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -38,23 +29,10 @@ namespace cleora {
 namespace {
 
 struct SpmmArgs {
-    const uint64_t *rowptr;
-    const uint32_t *col;
-    const float *val;
+    RowSchedule s;
     const float *x;
     uint64_t ldx;
     uint64_t x_bytes;      // span of x (whole-matrix buffer descriptor of the sub-wave hot path)
-    uint64_t n_items;      // hub segments + rows
-    uint64_t n_segments;
-    uint32_t hub_threshold;
-    // hub kernels
-    const uint32_t *seg_row;
-    const uint64_t *seg_begin;
-    uint32_t hub_segment;
-    const uint32_t *hub_rows;
-    const uint64_t *hub_seg_first;
-    float *partial;
-    const uint32_t *mid_rows;     // reference-order schedule: the first n_segments items are these rows (longest first), not segments
     // in-order hub kernel
     const uint32_t *hub_by_len;   // hub indices, longest row first
     uint64_t nnz;
@@ -63,139 +41,61 @@ struct SpmmArgs {
     RowArgs r;
 };
 
-// One gathered row.  HOT: bit 31 of the column index marks a frequently referenced row; those are
-// loaded with the default cache policy and every other (cold) row non-temporally, so the cold stream
-// does not evict the hot set (hot.hip: -10 % at C3).  The
-// policy is an immediate of buffer_load, so the row goes through a buffer descriptor: built from the
-// (wave-uniform) row pointer when a whole wavefront owns the row — its num_records = d*4 also does
-// the tail bounds check — or spanning the whole matrix (< 4 GiB) for sub-wave groups.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+// The f32 source of the edge loop: a gathered row is V chunks of W floats.  Without hot marks it is loaded with plain loads
+// (load_row); with them through gather_buffer, whose dwords are the floats.
+template <int kG, int kV, int kW, bool FULL, bool HOT>
+struct RowsF32 {
+    static constexpr int G = kG, V = kV, W = kW;
+    static constexpr int U = (8 / V) > 0 ? (8 / V) : 1;
+    using row_t = float[V][W];
 
-template <int G, int V, int W, bool FULL, bool HOT>
-__device__ __forceinline__ void gather_row(const SpmmArgs &a, uint32_t c, int gl, uint32_t d,
-                                           float (&r)[V][W]) {
-    if constexpr (!HOT) {
-        load_row<G, V, W, FULL>(a.x + (uint64_t)c * a.ldx, gl, d, r);
-    } else {
-        static_assert(W == 4, "hot policy is implemented for the float4 path");
-        const uint32_t cc = c & 0x7fffffffu;
-        const bool hot = (c >> 31) != 0;
-        if constexpr (G == 64) {
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)(a.x + (uint64_t)cc * a.ldx), 0,
-                                                              (int)(d * 4u), 0x00020000);
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const int off = (v * 64 + gl) * 16;
-                u32x4 t;
-                if (hot) t = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-                else t = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 2);       // aux 2 = nt
-                r[v][0] = __uint_as_float(t.x); r[v][1] = __uint_as_float(t.y);
-                r[v][2] = __uint_as_float(t.z); r[v][3] = __uint_as_float(t.w);
-            }
+    static __device__ __forceinline__ void gather(const SpmmArgs &a, uint32_t c, int gl, uint32_t d, row_t &r) {
+        if constexpr (!HOT) {
+            load_row<G, V, W, FULL>(a.x + (uint64_t)c * a.ldx, gl, d, r);
         } else {
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, (int)(uint32_t)a.x_bytes, 0x00020000);
+            static_assert(W == 4, "hot policy is implemented for the float4 path");
+            u32x4 t[V];
+            gather_buffer<G, V, 16, FULL, true>(a.x, a.ldx, a.x_bytes, c, gl, d, t);
 #pragma unroll
             for (int v = 0; v < V; ++v) {
-                const uint32_t j = (uint32_t)(v * G + gl) * 4u;
-                const int off = (int)((uint32_t)((uint64_t)cc * a.ldx + j) * 4u);
-                u32x4 t = {0u, 0u, 0u, 0u};
-                if (FULL || j < d) {
-                    if (hot) t = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-                    else t = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 2);
-                }
-                r[v][0] = __uint_as_float(t.x); r[v][1] = __uint_as_float(t.y);
-                r[v][2] = __uint_as_float(t.z); r[v][3] = __uint_as_float(t.w);
+                r[v][0] = __uint_as_float(t[v].x); r[v][1] = __uint_as_float(t[v].y);
+                r[v][2] = __uint_as_float(t[v].z); r[v][3] = __uint_as_float(t[v].w);
             }
         }
     }
-}
-
-// acc += sum over edges [beg, end) in stored order.  For G == 64 beg/end are wave-uniform.
-template <int G, int V, int W, bool FULL, bool HOT = false>
-__device__ __forceinline__ void accumulate(const SpmmArgs &a, uint64_t beg, uint64_t end, int gl,
-                                           int gbase, float (&acc)[V][W]) {
-    constexpr int U = (8 / V) > 0 ? (8 / V) : 1;
-    const uint32_t d = a.r.d;
-    for (uint64_t e = beg; e < end; e += G) {
-        const uint32_t cnt = (end - e) < (uint64_t)G ? (uint32_t)(end - e) : (uint32_t)G;
-        uint32_t cv = 0;
-        float wv = 0.f;
-        if ((uint32_t)gl < cnt) {
-            cv = a.col[e + gl];                       // (loaded non-temporally the edge stream measured no better in the fast placement
-            wv = a.val[e + gl];                       //  class and 1-2 ms worse in the slow one: scripts/r06/store_policy_probe.py)
-        }
-        uint32_t k = 0;
-        {
-            for (; k + U <= cnt; k += U) {
-                float r[U][V][W];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const uint32_t c = bcast_u32<G>(cv, k + u, gbase);
-                    gather_row<G, V, W, FULL, HOT>(a, c, gl, d, r[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const float w = bcast_f32<G>(wv, k + u, gbase);
-#pragma unroll
-                    for (int v = 0; v < V; ++v)
-#pragma unroll
-                        for (int q = 0; q < W; ++q) acc[v][q] = fadd(acc[v][q], fmul(w, r[u][v][q]));
-                }
-            }
-        }
-        for (; k < cnt; ++k) {
-            float r[V][W];
-            const uint32_t c = bcast_u32<G>(cv, k, gbase);
-            const float w = bcast_f32<G>(wv, k, gbase);
-            gather_row<G, V, W, FULL, HOT>(a, c, gl, d, r);
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-#pragma unroll
-                for (int q = 0; q < W; ++q) acc[v][q] = fadd(acc[v][q], fmul(w, r[v][q]));
-        }
-    }
-}
-
-template <int G, int V, int W>
-__device__ __forceinline__ void zero(float (&acc)[V][W]) {
-#pragma unroll
-    for (int v = 0; v < V; ++v)
-#pragma unroll
-        for (int q = 0; q < W; ++q) acc[v][q] = 0.f;
-}
+    static __device__ __forceinline__ float elem(const row_t &r, int v, int q) { return r[v][q]; }
+};
 
 // ---- main kernel ---------------------------------------------------------------------------
-// Work items: first the hub SEGMENTS (so the longest work starts first), then one item per row.
-// A segment item writes its partial sum to scratch; a row item runs the epilogue and writes Y.
 template <int G, int V, int W, bool FULL, bool HOT = false>
 __global__ __launch_bounds__(256) void spmm_rows_kernel(const SpmmArgs a) {
     const int lane = threadIdx.x & 63;
     const int gl = lane & (G - 1);
     const int gbase = lane & ~(G - 1);
     uint64_t item = CLEORA_LINEAR_BLOCK() * (256 / G) + (threadIdx.x / G);
-    bool active = item < a.n_items;
+    bool active = item < a.s.n_items;
     if constexpr (G == 64) {
         if (!active) return;
         item = uniform_u64(item);
     }
-    const bool is_mid = a.mid_rows != nullptr && item < a.n_segments;      // a long row scheduled first: a whole row like any other
-    const bool is_seg = a.mid_rows == nullptr && item < a.n_segments;
+    const bool is_mid = a.s.mid_rows != nullptr && item < a.s.n_segments;
+    const bool is_seg = a.s.mid_rows == nullptr && item < a.s.n_segments;
     uint64_t row = 0, beg = 0, end = 0;
     if (active) {
         if (is_mid) {
-            row = a.mid_rows[item];
-            beg = a.rowptr[row];
-            end = a.rowptr[row + 1];
+            row = a.s.mid_rows[item];
+            beg = a.s.rowptr[row];
+            end = a.s.rowptr[row + 1];
         } else if (is_seg) {
-            row = a.seg_row[item];
-            beg = a.seg_begin[item];
-            const uint64_t rend = a.rowptr[row + 1];
-            end = beg + a.hub_segment < rend ? beg + a.hub_segment : rend;
+            row = a.s.seg_row[item];
+            beg = a.s.seg_begin[item];
+            const uint64_t rend = a.s.rowptr[row + 1];
+            end = beg + a.s.hub_segment < rend ? beg + a.s.hub_segment : rend;
         } else {
-            row = item - a.n_segments;
-            beg = a.rowptr[row];
-            end = a.rowptr[row + 1];
-            if (end - beg > a.hub_threshold) active = false;  // hub row: its segments own it
+            row = item - a.s.n_segments;
+            beg = a.s.rowptr[row];
+            end = a.s.rowptr[row + 1];
+            if (end - beg > a.s.hub_threshold) active = false;
         }
     }
     if constexpr (G == 64) {
@@ -207,10 +107,10 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(const SpmmArgs a) {
         beg = end = 0;
     }
     float acc[V][W];
-    zero<G, V, W>(acc);
-    accumulate<G, V, W, FULL, HOT>(a, beg, end, gl, gbase, acc);
+    zero(acc);
+    accumulate<RowsF32<G, V, W, FULL, HOT>>(a, beg, end, gl, gbase, acc);
     if (active) {
-        if (is_seg) store_row<G, V, W, FULL>(a.partial + item * (uint64_t)a.r.d, gl, a.r.d, acc);
+        if (is_seg) store_row<G, V, W, FULL>(a.s.partial + item * (uint64_t)a.r.d, gl, a.r.d, acc);
         else finish_row<G, V, W, FULL>(a.r, row, gl, gbase, acc);
     }
 }
@@ -228,20 +128,20 @@ __global__ __launch_bounds__(256) void hub_finish_kernel(const SpmmArgs a) {
     const int gbase = lane & ~(G - 1);
     const int grp = threadIdx.x / G;
     const uint64_t h = blockIdx.x;
-    const uint64_t row = a.hub_rows[h];
-    const uint64_t s0 = a.hub_seg_first[h], s1 = a.hub_seg_first[h + 1];
+    const uint64_t row = a.s.hub_rows[h];
+    const uint64_t s0 = a.s.hub_seg_first[h], s1 = a.s.hub_seg_first[h + 1];
     const uint64_t per = (s1 - s0 + NG - 1) / NG;
     const uint64_t b = s0 + grp * per < s1 ? s0 + grp * per : s1;
     const uint64_t e = b + per < s1 ? b + per : s1;
     const uint32_t d = a.r.d;
     float acc[V][W];
-    zero<G, V, W>(acc);
+    zero(acc);
     constexpr int U = (8 / V) > 0 ? (8 / V) : 1;
     uint64_t s = b;
     for (; s + U <= e; s += U) {
         float p[U][V][W];
 #pragma unroll
-        for (int u = 0; u < U; ++u) load_row<G, V, W, false>(a.partial + (s + u) * (uint64_t)d, gl, d, p[u]);
+        for (int u = 0; u < U; ++u) load_row<G, V, W, false>(a.s.partial + (s + u) * (uint64_t)d, gl, d, p[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -251,7 +151,7 @@ __global__ __launch_bounds__(256) void hub_finish_kernel(const SpmmArgs a) {
     }
     for (; s < e; ++s) {
         float p[V][W];
-        load_row<G, V, W, false>(a.partial + s * (uint64_t)d, gl, d, p);
+        load_row<G, V, W, false>(a.s.partial + s * (uint64_t)d, gl, d, p);
 #pragma unroll
         for (int v = 0; v < V; ++v)
 #pragma unroll
@@ -310,8 +210,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void hu
     const uint64_t item = CLEORA_LINEAR_BLOCK();
     const uint32_t k = (uint32_t)(item / a.n_slabs), slab = (uint32_t)(item - (uint64_t)k * a.n_slabs);
     const uint32_t h = a.hub_by_len[k + a.hub_first];
-    const uint64_t row = a.hub_rows[h];
-    const uint64_t beg = a.rowptr[row], n = a.rowptr[row + 1] - beg;
+    const uint64_t row = a.s.hub_rows[h];
+    const uint64_t beg = a.s.rowptr[row], n = a.s.rowptr[row + 1] - beg;
     const uint32_t d = a.r.d;
     const uint32_t coff = QUAD ? slab * (uint32_t)COLS + (uint32_t)(lane >> 4) * (4u * (QUAD ? L : 1)) + (uint32_t)((lane & 15) % (QUAD ? L : 1)) * 4u
                                : slab * 64u + (uint32_t)lane;
@@ -320,8 +220,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void hu
 
     const uint64_t left_bytes = (a.nnz - beg) * 4u;
     const int records = (int)(left_bytes > 0xfffffffcull ? 0xfffffffcu : (uint32_t)left_bytes);
-    const auto rs_col = __builtin_amdgcn_make_buffer_rsrc((void *)(a.col + beg), 0, records, 0x00020000);
-    const auto rs_val = __builtin_amdgcn_make_buffer_rsrc((void *)(a.val + beg), 0, records, 0x00020000);
+    const auto rs_col = __builtin_amdgcn_make_buffer_rsrc((void *)(a.s.col + beg), 0, records, 0x00020000);
+    const auto rs_val = __builtin_amdgcn_make_buffer_rsrc((void *)(a.s.val + beg), 0, records, 0x00020000);
     // entries past the row's end are the next rows' (valid gather addresses, never consumed) or, past the array, zero
     u32x4 pc[NF ? NF : 1], pv[NF ? NF : 1];
     auto fetch = [&](uint64_t chunk) {
@@ -425,7 +325,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void hu
     }
     const uint32_t tail = (uint32_t)(n - whole_chunks * CH);
     if (tail) chunk_body(std::false_type{}, (int)(whole_chunks & 1), tail);
-    float *p = a.partial + (uint64_t)h * d + coff;
+    float *p = a.s.partial + (uint64_t)h * d + coff;
     if constexpr (QUAD) {
         if (in_range && (uint32_t)q == (uint32_t)((n - 1) % EPS)) *reinterpret_cast<float4 *>(p) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     } else {
@@ -469,8 +369,8 @@ __global__ __launch_bounds__(512) void hub_chain_kernel(const SpmmArgs a) {
     const uint64_t item = CLEORA_LINEAR_BLOCK();
     const uint32_t k = (uint32_t)(item / a.n_slabs), slab = (uint32_t)(item - (uint64_t)k * a.n_slabs);
     const uint32_t h = a.hub_by_len[k];
-    const uint64_t row = a.hub_rows[h];
-    const uint64_t beg = a.rowptr[row], n = a.rowptr[row + 1] - beg;
+    const uint64_t row = a.s.hub_rows[h];
+    const uint64_t beg = a.s.rowptr[row], n = a.s.rowptr[row + 1] - beg;
     const uint32_t d = a.r.d;
     const uint64_t nchunks = (n + HC_CH - 1) / HC_CH;
     // interval j: producers make chunk j, the consumer adds chunk j - 1; whole trips of D intervals (the surplus ones are idle)
@@ -513,7 +413,7 @@ __global__ __launch_bounds__(512) void hub_chain_kernel(const SpmmArgs a) {
             hc_barrier();
         }
         const uint32_t c = slab * 64u + (uint32_t)lane;
-        if (c < d) a.partial[(uint64_t)h * d + c] = acc;
+        if (c < d) a.s.partial[(uint64_t)h * d + c] = acc;
         return;
     }
     // ---- producers: lane = (edge quad qr | four columns) -------------------------------------------------------------
@@ -522,8 +422,8 @@ __global__ __launch_bounds__(512) void hub_chain_kernel(const SpmmArgs a) {
     const float *xb = a.x + (coff < d ? coff : 0u);                               // (columns past d: a valid address; the consumer never stores them)
     const uint64_t left_bytes = (a.nnz - beg) * 4u;
     const int records = (int)(left_bytes > 0xfffffffcull ? 0xfffffffcu : (uint32_t)left_bytes);
-    const auto rs_col = __builtin_amdgcn_make_buffer_rsrc((void *)(a.col + beg), 0, records, 0x00020000);
-    const auto rs_val = __builtin_amdgcn_make_buffer_rsrc((void *)(a.val + beg), 0, records, 0x00020000);
+    const auto rs_col = __builtin_amdgcn_make_buffer_rsrc((void *)(a.s.col + beg), 0, records, 0x00020000);
+    const auto rs_val = __builtin_amdgcn_make_buffer_rsrc((void *)(a.s.val + beg), 0, records, 0x00020000);
     // this lane's four edges of chunk c: c * 112 + 16 p + 4 qr + u; entries past the row's end are the next rows' (valid gather
     // addresses, products never added) or, past the array, zero
     const uint32_t lane_edge = (uint32_t)(16 * p + 4 * qr);
@@ -576,8 +476,8 @@ __global__ __launch_bounds__(256) void hub_epilogue_kernel(const SpmmArgs a, uin
     const uint64_t h = (uint64_t)blockIdx.x * (256 / G) + (threadIdx.x / G);
     if (h >= n_hub_rows) return;
     float acc[V][W];
-    load_row<G, V, W, false>(a.partial + h * (uint64_t)a.r.d, gl, a.r.d, acc);
-    finish_row<G, V, W, false>(a.r, a.hub_rows[h], gl, gbase, acc);
+    load_row<G, V, W, false>(a.s.partial + h * (uint64_t)a.r.d, gl, a.r.d, acc);
+    finish_row<G, V, W, false>(a.r, a.s.hub_rows[h], gl, gbase, acc);
 }
 
 // ---- stand-alone row epilogue (l2_normalize_inplace & friends) --------------------------
@@ -838,7 +738,7 @@ int propagate_panel(const cleora_graph *g, SpmmArgs a, bool w4, bool segmented, 
         CL_HIP(hipEventRecord(g->hub_fork, stream));
         CL_HIP(hipStreamWaitEvent(g->hub_stream, g->hub_fork, 0));
         a.hub_by_len = g->hub_by_len;
-        a.hub_rows = g->io_rows;
+        a.s.hub_rows = g->io_rows;
         a.nnz = g->nnz;
         // the few longest rows: one 8-wave block per (row, 64-column slab) — products by producer waves, the chain by a wave that only adds
         const uint64_t n_chain = w4 ? hub_chain_rows(g, d) : 0;
@@ -865,12 +765,12 @@ int propagate_panel(const cleora_graph *g, SpmmArgs a, bool w4, bool segmented, 
         CL_HIP(hipEventRecord(g->hub_join, g->hub_stream));
     }
     mark(g, stream);
-    a.hub_rows = g->hub_rows;
-    a.mid_rows = inorder ? g->mid_rows : nullptr;
-    a.n_segments = inorder ? g->n_mid_rows : g->n_hub_segments;
-    if (inorder && !g->n_mid_rows) a.mid_rows = nullptr;
-    a.n_items = a.n_segments + g->n_rows;
-    if (ok && a.n_items) {
+    a.s.hub_rows = g->hub_rows;
+    a.s.mid_rows = inorder ? g->mid_rows : nullptr;
+    a.s.n_segments = inorder ? g->n_mid_rows : g->n_hub_segments;
+    if (inorder && !g->n_mid_rows) a.s.mid_rows = nullptr;
+    a.s.n_items = a.s.n_segments + g->n_rows;
+    if (ok && a.s.n_items) {
         ok = dispatch_shape(d, w4, [&](auto G, auto V, auto W, auto FULL) {
             constexpr int kG = decltype(G)::value, kV = decltype(V)::value, kW = decltype(W)::value;
             constexpr bool kFull = decltype(FULL)::value != 0;
@@ -880,14 +780,14 @@ int propagate_panel(const cleora_graph *g, SpmmArgs a, bool w4, bool segmented, 
                 const uint32_t *hot = (kG == 64 || a.x_bytes < (1ull << 32)) ? ensure_hot_cols(g, d, a.ldx, stream) : nullptr;
                 if (hot) {
                     SpmmArgs h = a;
-                    h.col = hot;
+                    h.s.col = hot;
                     hipLaunchKernelGGL((spmm_rows_kernel<kG, kV, kW, kFull, true>),
-                                       grid_for(h.n_items, 256 / kG), dim3(256), 0, stream, h);
+                                       grid_for(h.s.n_items, 256 / kG), dim3(256), 0, stream, h);
                     return;
                 }
             }
             hipLaunchKernelGGL((spmm_rows_kernel<kG, kV, kW, kFull, false>),
-                               grid_for(a.n_items, 256 / kG), dim3(256), 0, stream, a);
+                               grid_for(a.s.n_items, 256 / kG), dim3(256), 0, stream, a);
         });
     }
     mark(g, stream);
@@ -949,19 +849,10 @@ int launch_propagate(const cleora_graph *g, int kind, const float *x, uint64_t l
     }
 
     SpmmArgs a{};
-    a.rowptr = g->rowptr;
-    a.col = g->col;
-    a.val = val_override ? val_override : g->val[kind];
+    a.s = make_schedule(g, val_override ? val_override : g->val[kind]);      // (propagate_panel picks the hub rows' schedule)
     a.x = x;
     a.ldx = ldx;
     a.x_bytes = g->n_cols * ldx * sizeof(float);
-    a.hub_threshold = g->hub_threshold;
-    a.seg_row = g->seg_row;
-    a.seg_begin = g->seg_begin;
-    a.hub_segment = g->hub_segment;
-    a.hub_rows = g->hub_rows;
-    a.hub_seg_first = g->hub_seg_first;
-    a.partial = g->hub_partial;
     a.r.y = y;
     a.r.ldy = ldy;
     a.r.x_self = x_self;

@@ -13,50 +13,36 @@
 //   * SQDIFF / SQDIFF64 are taken AFTER that rounding, between the widened stored value and the widened x_self: the RMSE of the
 //     iterates the loop actually holds.
 //
-// Mapping:
-//   * d >= 256: a whole wavefront owns one output row; the column index arrives in an SGPR (v_readlane) and the gathered row goes
-//     through a per-row buffer descriptor with num_records = d * 2, which does the tail check and carries the per-edge cache policy
-//     (hot.hip's bit-31 marks) as an immediate.  A lane loads C = 4 halfs (8 bytes) per chunk, or C = 8 (16 bytes) where the row is
-//     >= 1 KiB and everything is 16-byte aligned;
+// Mapping: the row kernel of spmm_rows.h (schedule of work items, edge loop, hot / cold gather).  What this file adds:
+//   * the f16 source policy: a lane loads C = 4 halfs (8 bytes) per chunk, or C = 8 (16 bytes) where the row is >= 1 KiB and
+//     everything is 16-byte aligned; at G = 64 the row always goes through the per-row buffer descriptor (num_records = d * 2 does the
+//     tail check), with the hot marks sized by row bytes (hot.hip);
 //   * 128 bytes of gathers per lane are in flight before the first use, 8 KiB per wavefront like the f32 kernel: U * V = 16 load
 //     instructions at C = 4 (16 edges of a d = 256 row), 8 at C = 8;
 //   * narrower d packs 64 / G rows per wavefront (G = 8, 16, 32 lanes per row, 8 bytes per lane);
-//   * rows longer than hub_threshold ALWAYS take the segmented schedule (what CLEORA_F_HUB_SEGMENTS selects in spmm.hip): their
-//     hub_segment-edge segments are the first work items, f32 partial sums go to the graph's hub_partial scratch and
-//     hub_finish_h_kernel adds them in a fixed order and runs the epilogue.  In-order f16 hub kernels are a follow-up.
+//   * rows longer than hub_threshold ALWAYS take the segmented schedule (what CLEORA_F_HUB_SEGMENTS selects in spmm.hip), finished by
+//     hub_finish_h_kernel with the f16 epilogue.  In-order f16 hub kernels are a follow-up.
 //
 // F32OUT variant (cleora_propagate_hf_dev; CLEORA_F_GATHER_F16 in the whitened loop): the same gather on an f16 X, but Y is f32 and
 // nothing is rounded on the way out — the loop's Z = A Y, whose input rows are normalised (|Y| <= 1) and whose output the projection
 // consumes in f32.  Same contract up to the epilogue (L2 / L1 / FASTNORM; no x_self flags); tests/test_gpu_gather_f16.py.
 #include "common.h"
 #include "row_epilogue.h"
+#include "spmm_rows.h"
 
 #include <type_traits>
 
 namespace cleora {
 namespace {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-template <int C> using raw_t = std::conditional_t<C == 4, u32x2, u32x4>;     // C halfs as they lie in memory
+template <int C> using halfs_t = raw_t<2 * C>;     // C halfs as they lie in memory
 
 struct SpmmHArgs {
-    const uint64_t *rowptr;
-    const uint32_t *col;
-    const float *val;
+    RowSchedule s;
     const uint16_t *x;
     uint64_t ldx;
     uint64_t x_bytes;      // span of x (whole-matrix buffer descriptor of the sub-wave hot path)
-    uint64_t n_items;      // hub segments + rows
-    uint64_t n_segments;
-    uint32_t hub_threshold;
-    const uint32_t *seg_row;
-    const uint64_t *seg_begin;
-    uint32_t hub_segment;
-    const uint32_t *hub_rows;
-    const uint64_t *hub_seg_first;
-    float *partial;
     uint16_t *y;
     uint64_t ldy;
     const uint16_t *x_self;
@@ -73,89 +59,31 @@ __device__ __forceinline__ uint32_t round_pair(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, p);
 }
 
-template <int C, int AUX>
-__device__ __forceinline__ raw_t<C> buffer_load(__amdgpu_buffer_rsrc_t rs, int off) {
-    if constexpr (C == 4) return __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, AUX);
-    else return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, AUX);
-}
+// The f16 source of the edge loop: a gathered row stays packed, V chunks of C halfs, until it is added.
+template <int kG, int kV, int C, bool HOT>
+struct RowsF16 {
+    static constexpr int G = kG, V = kV, W = C;
+    static constexpr int LOADS = C == 4 ? 16 : 8;                     // 128 bytes per lane in flight
+    static constexpr int U = (LOADS / V) > 0 ? (LOADS / V) : 1;
+    using row_t = halfs_t<C>[V];
+    static_assert(G == 64 || C == 4, "sub-wave groups load 8 bytes per lane");
 
-// One gathered row, still packed.  HOT: bit 31 of the column index marks a frequently referenced row (hot.hip); the others are
-// loaded non-temporally (aux 2).
-template <int G, int V, int C, bool HOT>
-__device__ __forceinline__ void gather_row_h(const SpmmHArgs &a, uint32_t c, int gl, uint32_t d, raw_t<C> (&r)[V]) {
-    const uint32_t cc = HOT ? (c & 0x7fffffffu) : c;
-    const bool cold = HOT && (c >> 31) == 0;
-    if constexpr (G == 64) {
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)(a.x + (uint64_t)cc * a.ldx), 0, (int)(d * 2u), 0x00020000);
+    static __device__ __forceinline__ void gather(const SpmmHArgs &a, uint32_t c, int gl, uint32_t d, row_t &r) {
+        if constexpr (G == 64 || HOT) {
+            gather_buffer<G, V, 2 * C, false, HOT>(a.x, a.ldx, a.x_bytes, c, gl, d, r);
+        } else {
 #pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const int off = (v * 64 + gl) * (C * 2);
-            if (cold) r[v] = buffer_load<C, 2>(rs, off);
-            else r[v] = buffer_load<C, 0>(rs, off);
-        }
-    } else {
-        static_assert(G == 64 || C == 4, "sub-wave groups load 8 bytes per lane");
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const uint32_t j = (uint32_t)(v * G + gl) * C;
-            raw_t<C> t = {};
-            if constexpr (HOT) {
-                const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, (int)(uint32_t)a.x_bytes, 0x00020000);
-                const int off = (int)((uint32_t)((uint64_t)cc * a.ldx + j) * 2u);
-                if (j < d) {
-                    if (cold) t = buffer_load<C, 2>(rs, off);
-                    else t = buffer_load<C, 0>(rs, off);
-                }
-            } else {
-                if (j < d) t = *reinterpret_cast<const raw_t<C> *>(a.x + (uint64_t)cc * a.ldx + j);
+            for (int v = 0; v < V; ++v) {
+                const uint32_t j = (uint32_t)(v * G + gl) * C;
+                halfs_t<C> t = {};
+                if (j < d) t = *reinterpret_cast<const halfs_t<C> *>(a.x + (uint64_t)c * a.ldx + j);
+                r[v] = t;
             }
-            r[v] = t;
         }
     }
-}
-
-// acc += w * row: every half widened exactly, separate multiply and add
-template <int V, int C>
-__device__ __forceinline__ void add_edge(float w, const raw_t<C> (&r)[V], float (&acc)[V][C]) {
-#pragma unroll
-    for (int v = 0; v < V; ++v)
-#pragma unroll
-        for (int i = 0; i < C / 2; ++i) {
-            acc[v][2 * i] = fadd(acc[v][2 * i], fmul(w, widen_lo(r[v][i])));
-            acc[v][2 * i + 1] = fadd(acc[v][2 * i + 1], fmul(w, widen_hi(r[v][i])));
-        }
-}
-
-// acc += sum over edges [beg, end) in stored order.  For G == 64 beg / end are wave-uniform.
-template <int G, int V, int C, bool HOT>
-__device__ __forceinline__ void accumulate_h(const SpmmHArgs &a, uint64_t beg, uint64_t end, int gl, int gbase,
-                                             float (&acc)[V][C]) {
-    constexpr int LOADS = C == 4 ? 16 : 8;                     // 128 bytes per lane in flight
-    constexpr int U = (LOADS / V) > 0 ? (LOADS / V) : 1;
-    const uint32_t d = a.r.d;
-    for (uint64_t e = beg; e < end; e += G) {
-        const uint32_t cnt = (end - e) < (uint64_t)G ? (uint32_t)(end - e) : (uint32_t)G;
-        uint32_t cv = 0;
-        float wv = 0.f;
-        if ((uint32_t)gl < cnt) {
-            cv = a.col[e + gl];
-            wv = a.val[e + gl];
-        }
-        uint32_t k = 0;
-        for (; k + U <= cnt; k += U) {
-            raw_t<C> r[U][V];
-#pragma unroll
-            for (int u = 0; u < U; ++u) gather_row_h<G, V, C, HOT>(a, bcast_u32<G>(cv, k + u, gbase), gl, d, r[u]);
-#pragma unroll
-            for (int u = 0; u < U; ++u) add_edge<V, C>(bcast_f32<G>(wv, k + u, gbase), r[u], acc);
-        }
-        for (; k < cnt; ++k) {
-            raw_t<C> r[V];
-            gather_row_h<G, V, C, HOT>(a, bcast_u32<G>(cv, k, gbase), gl, d, r);
-            add_edge<V, C>(bcast_f32<G>(wv, k, gbase), r, acc);
-        }
-    }
-}
+    // column q of chunk v, widened exactly
+    static __device__ __forceinline__ float elem(const row_t &r, int v, int q) { return (q & 1) ? widen_hi(r[v][q / 2]) : widen_lo(r[v][q / 2]); }
+};
 
 // The row epilogue on f16 storage: x_self widened, the f32 arithmetic of row_epilogue.h, one rounding, SQDIFF on what is stored.
 template <int G, int V, int C>
@@ -168,8 +96,8 @@ __device__ __forceinline__ void finish_row_h(const SpmmHArgs &a, uint64_t row, i
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const uint32_t j = (uint32_t)(v * G + gl) * C;
-            raw_t<C> t = {};
-            if (j < d) t = *reinterpret_cast<const raw_t<C> *>(p + j);
+            halfs_t<C> t = {};
+            if (j < d) t = *reinterpret_cast<const halfs_t<C> *>(p + j);
 #pragma unroll
             for (int i = 0; i < C / 2; ++i) {
                 xs[v][2 * i] = widen_lo(t[i]);
@@ -179,7 +107,7 @@ __device__ __forceinline__ void finish_row_h(const SpmmHArgs &a, uint64_t row, i
     }
     blend_and_normalize<G, V, C>(ra, row, gl, gbase, acc, xs);
 
-    raw_t<C> out[V];
+    halfs_t<C> out[V];
 #pragma unroll
     for (int v = 0; v < V; ++v)
 #pragma unroll
@@ -210,8 +138,8 @@ __device__ __forceinline__ void finish_row_h(const SpmmHArgs &a, uint64_t row, i
     for (int v = 0; v < V; ++v) {
         const uint32_t j = (uint32_t)(v * G + gl) * C;
         if (j < d) {
-            if (nt) __builtin_nontemporal_store(out[v], reinterpret_cast<raw_t<C> *>(yr + j));
-            else *reinterpret_cast<raw_t<C> *>(yr + j) = out[v];
+            if (nt) __builtin_nontemporal_store(out[v], reinterpret_cast<halfs_t<C> *>(yr + j));
+            else *reinterpret_cast<halfs_t<C> *>(yr + j) = out[v];
         }
     }
 }
@@ -245,32 +173,31 @@ __device__ __forceinline__ void finish_row_hf(const SpmmHArgs &a, uint64_t row, 
 }
 
 // ---- main kernel ---------------------------------------------------------------------------
-// Work items: first the hub SEGMENTS (so the longest work starts first), then one item per row.  A segment item writes its f32
-// partial sum to scratch; a row item runs the epilogue and writes Y (f16, or f32 with F32OUT).
+// A row item writes Y as f16, or as f32 with F32OUT.
 template <int G, int V, int C, bool HOT, bool F32OUT = false>
 __global__ __launch_bounds__(256) void spmm_rows_h_kernel(const SpmmHArgs a) {
     const int lane = threadIdx.x & 63;
     const int gl = lane & (G - 1);
     const int gbase = lane & ~(G - 1);
     uint64_t item = CLEORA_LINEAR_BLOCK() * (256 / G) + (threadIdx.x / G);
-    bool active = item < a.n_items;
+    bool active = item < a.s.n_items;
     if constexpr (G == 64) {
         if (!active) return;
         item = uniform_u64(item);
     }
-    const bool is_seg = item < a.n_segments;
+    const bool is_seg = item < a.s.n_segments;
     uint64_t row = 0, beg = 0, end = 0;
     if (active) {
         if (is_seg) {
-            row = a.seg_row[item];
-            beg = a.seg_begin[item];
-            const uint64_t rend = a.rowptr[row + 1];
-            end = beg + a.hub_segment < rend ? beg + a.hub_segment : rend;
+            row = a.s.seg_row[item];
+            beg = a.s.seg_begin[item];
+            const uint64_t rend = a.s.rowptr[row + 1];
+            end = beg + a.s.hub_segment < rend ? beg + a.s.hub_segment : rend;
         } else {
-            row = item - a.n_segments;
-            beg = a.rowptr[row];
-            end = a.rowptr[row + 1];
-            if (end - beg > a.hub_threshold) active = false;  // hub row: its segments own it
+            row = item - a.s.n_segments;
+            beg = a.s.rowptr[row];
+            end = a.s.rowptr[row + 1];
+            if (end - beg > a.s.hub_threshold) active = false;
         }
     }
     if constexpr (G == 64) {
@@ -283,13 +210,13 @@ __global__ __launch_bounds__(256) void spmm_rows_h_kernel(const SpmmHArgs a) {
     }
     float acc[V][C];
 #pragma unroll
-    for (int v = 0; v < V; ++v)
+    for (int v = 0; v < V; ++v)                                       // (not zero(acc): with it the d = 1024 shapes took 116 VGPRs for 71)
 #pragma unroll
         for (int q = 0; q < C; ++q) acc[v][q] = 0.f;
-    accumulate_h<G, V, C, HOT>(a, beg, end, gl, gbase, acc);
+    accumulate<RowsF16<G, V, C, HOT>>(a, beg, end, gl, gbase, acc);
     if (!active) return;
     if (is_seg) {
-        float *p = a.partial + item * (uint64_t)a.r.d;
+        float *p = a.s.partial + item * (uint64_t)a.r.d;
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const uint32_t j = (uint32_t)(v * G + gl) * C;
@@ -315,23 +242,20 @@ __global__ __launch_bounds__(256) void hub_finish_h_kernel(const SpmmHArgs a) {
     const int gl = threadIdx.x & 63;
     const int grp = threadIdx.x >> 6;
     const uint64_t h = blockIdx.x;
-    const uint64_t row = a.hub_rows[h];
-    const uint64_t s0 = a.hub_seg_first[h], s1 = a.hub_seg_first[h + 1];
+    const uint64_t row = a.s.hub_rows[h];
+    const uint64_t s0 = a.s.hub_seg_first[h], s1 = a.s.hub_seg_first[h + 1];
     const uint64_t per = (s1 - s0 + 3) / 4;
     const uint64_t b = s0 + grp * per < s1 ? s0 + grp * per : s1;
     const uint64_t e = b + per < s1 ? b + per : s1;
     const uint32_t d = a.r.d;
     float acc[V][4];
-#pragma unroll
-    for (int v = 0; v < V; ++v)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[v][q] = 0.f;
+    zero(acc);
     constexpr int U = 8 / V;
     uint64_t s = b;
     for (; s + U <= e; s += U) {
         float p[U][V][4];
 #pragma unroll
-        for (int u = 0; u < U; ++u) load_row<64, V, 4, false>(a.partial + (s + u) * (uint64_t)d, gl, d, p[u]);
+        for (int u = 0; u < U; ++u) load_row<64, V, 4, false>(a.s.partial + (s + u) * (uint64_t)d, gl, d, p[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -341,7 +265,7 @@ __global__ __launch_bounds__(256) void hub_finish_h_kernel(const SpmmHArgs a) {
     }
     for (; s < e; ++s) {
         float p[V][4];
-        load_row<64, V, 4, false>(a.partial + s * (uint64_t)d, gl, d, p);
+        load_row<64, V, 4, false>(a.s.partial + s * (uint64_t)d, gl, d, p);
 #pragma unroll
         for (int v = 0; v < V; ++v)
 #pragma unroll
@@ -401,21 +325,10 @@ static int launch_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t
     }
 
     SpmmHArgs a{};
-    a.rowptr = g->rowptr;
-    a.col = g->col;
-    a.val = g->val[kind];
+    a.s = make_schedule(g, g->val[kind]);
     a.x = x;
     a.ldx = ldx;
     a.x_bytes = g->n_cols * ldx * sizeof(uint16_t);
-    a.n_segments = g->n_hub_segments;
-    a.n_items = a.n_segments + g->n_rows;
-    a.hub_threshold = g->hub_threshold;
-    a.seg_row = g->seg_row;
-    a.seg_begin = g->seg_begin;
-    a.hub_segment = g->hub_segment;
-    a.hub_rows = g->hub_rows;
-    a.hub_seg_first = g->hub_seg_first;
-    a.partial = g->hub_partial;
     if constexpr (F32OUT) a.y32 = static_cast<float *>(y);
     else a.y = static_cast<uint16_t *>(y);
     a.ldy = ldy;
@@ -433,13 +346,13 @@ static int launch_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t
                       (!x_self || aligned_to(x_self, 16));
     dispatch_shape_h(d, wide, [&](auto G, auto V, auto C) {
         constexpr int kG = decltype(G)::value, kV = decltype(V)::value, kC = decltype(C)::value;
-        const dim3 grid = grid_1d_as_2d((a.n_items + 256 / kG - 1) / (256 / kG));
+        const dim3 grid = grid_1d_as_2d((a.s.n_items + 256 / kG - 1) / (256 / kG));
         // hot-column cache policy, sized by row BYTES: needs the marked column copy and, for sub-wave groups, a matrix that one
         // buffer descriptor can span
         const uint32_t *hot = (kG == 64 || a.x_bytes < (1ull << 32)) ? ensure_hot_cols(g, d, ldx, stream, sizeof(uint16_t)) : nullptr;
         if (hot) {
             SpmmHArgs h = a;
-            h.col = hot;
+            h.s.col = hot;
             hipLaunchKernelGGL((spmm_rows_h_kernel<kG, kV, kC, true, F32OUT>), grid, dim3(256), 0, stream, h);
         } else {
             hipLaunchKernelGGL((spmm_rows_h_kernel<kG, kV, kC, false, F32OUT>), grid, dim3(256), 0, stream, a);
@@ -456,16 +369,25 @@ static int launch_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t
     return CLEORA_OK;
 }
 
-int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, uint16_t *y, uint64_t ldy,
-                       uint32_t flags, float rw, const uint16_t *x_self, double *row_sqdiff, hipStream_t stream) {
+// What both entry points require of the graph, the f16 x and the shape.
+static int check_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, const void *y, uint64_t ldy, const char *d_msg,
+                   const char *ld_msg) {
     CL_REQUIRE(g != nullptr, "graph handle is NULL");
     CL_REQUIRE(kind == CLEORA_LEFT || kind == CLEORA_SYMMETRIC, "unknown markov_type");
     CL_REQUIRE(g->val[kind] != nullptr, "graph has no values for this markov_type");
     CL_REQUIRE(d > 0 && ldx >= d && ldy >= d, "bad d / leading dimension");
     CL_REQUIRE(x != nullptr && y != nullptr, "x / y is NULL");
-    CL_REQUIRE(x != y, "x and y must not alias");
-    CL_REQUIRE(d % 4 == 0 && d <= kMaxDH, "f16 rows: d must be a multiple of 4, at most 2048");
-    CL_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "f16 rows: leading dimensions must be multiples of 4");
+    CL_REQUIRE((const void *)x != y, "x and y must not alias");
+    CL_REQUIRE(d % 4 == 0 && d <= kMaxDH, d_msg);
+    CL_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, ld_msg);
+    return CLEORA_OK;
+}
+
+int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, uint16_t *y, uint64_t ldy,
+                       uint32_t flags, float rw, const uint16_t *x_self, double *row_sqdiff, hipStream_t stream) {
+    if (int rc = check_h(g, kind, x, ldx, d, y, ldy, "f16 rows: d must be a multiple of 4, at most 2048",
+                         "f16 rows: leading dimensions must be multiples of 4"))
+        return rc;
     CL_REQUIRE(!(flags & (CLEORA_F_ROWSQ | CLEORA_F_SCALE | CLEORA_F_ROWSQ_CONT)), "f16 rows: ROWSQ / SCALE / ROWSQ_CONT are not served");
     CL_REQUIRE(!((flags & CLEORA_F_L1NORM) && (flags & CLEORA_F_L2NORM)), "L1NORM is exclusive with L2NORM");
     if ((flags & CLEORA_F_RESIDUAL) && !(rw > 0.0f && (rw < 1.0f || (flags & CLEORA_F_BLEND_ANY)))) flags &= ~CLEORA_F_RESIDUAL;
@@ -482,14 +404,9 @@ int launch_propagate_h(const cleora_graph *g, int kind, const uint16_t *x, uint6
 // y (f32) = epilogue(A widen(x)): the gather of launch_propagate_h, nothing rounded on the way out.  flags: L2NORM / L1NORM / FASTNORM.
 int launch_propagate_hf(const cleora_graph *g, int kind, const uint16_t *x, uint64_t ldx, uint32_t d, float *y, uint64_t ldy,
                         uint32_t flags, hipStream_t stream) {
-    CL_REQUIRE(g != nullptr, "graph handle is NULL");
-    CL_REQUIRE(kind == CLEORA_LEFT || kind == CLEORA_SYMMETRIC, "unknown markov_type");
-    CL_REQUIRE(g->val[kind] != nullptr, "graph has no values for this markov_type");
-    CL_REQUIRE(d > 0 && ldx >= d && ldy >= d, "bad d / leading dimension");
-    CL_REQUIRE(x != nullptr && y != nullptr, "x / y is NULL");
-    CL_REQUIRE((const void *)x != (const void *)y, "x and y must not alias");
-    CL_REQUIRE(d % 4 == 0 && d <= kMaxDH, "f16 gather: d must be a multiple of 4, at most 2048");
-    CL_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "f16 gather: leading dimensions must be multiples of 4");
+    if (int rc = check_h(g, kind, x, ldx, d, y, ldy, "f16 gather: d must be a multiple of 4, at most 2048",
+                         "f16 gather: leading dimensions must be multiples of 4"))
+        return rc;
     CL_REQUIRE(!(flags & (CLEORA_F_RESIDUAL | CLEORA_F_SQDIFF | CLEORA_F_ROWSQ | CLEORA_F_SCALE | CLEORA_F_ROWSQ_CONT)),
                "f16 gather into f32 rows: RESIDUAL / SQDIFF / ROWSQ / SCALE / ROWSQ_CONT are not served");
     CL_REQUIRE(!((flags & CLEORA_F_L1NORM) && (flags & CLEORA_F_L2NORM)), "L1NORM is exclusive with L2NORM");
