@@ -47,6 +47,9 @@ template <int kG, int kV, int kW, bool FULL, bool HOT>
 struct RowsF32 {
     static constexpr int G = kG, V = kV, W = kW;
     static constexpr int U = (8 / V) > 0 ? (8 / V) : 1;
+    // every shape whose occupancy the batched tail leaves alone (scripts/kernel_resources.py): not 16 lanes per row with hot marks
+    // (6 -> 5 waves per SIMD) and not 8 lanes per row with a partial last chunk (7 -> 6)
+    static constexpr bool BATCH_TAIL = G >= 32 || (G == 16 && !HOT) || (G == 8 && FULL);
     using row_t = float[V][W];
 
     static __device__ __forceinline__ void gather(const SpmmArgs &a, uint32_t c, int gl, uint32_t d, row_t &r) {
@@ -149,13 +152,22 @@ __global__ __launch_bounds__(256) void hub_finish_kernel(const SpmmArgs a) {
 #pragma unroll
                 for (int q = 0; q < W; ++q) acc[v][q] = fadd(acc[v][q], p[u][v][q]);
     }
-    for (; s < e; ++s) {
-        float p[V][W];
-        load_row<G, V, W, false>(a.s.partial + s * (uint64_t)d, gl, d, p);
+    if constexpr (U > 1) {
+        if (s < e) {                                   // the last e - s < U partials: loaded together (spmm_rows.h, BATCH_TAIL), added in order
+            const uint32_t m = (uint32_t)(e - s);
+            float p[U - 1][V][W] = {};
 #pragma unroll
-        for (int v = 0; v < V; ++v)
+            for (int u = 0; u < U - 1; ++u)
+                if ((uint32_t)u < m) load_row<G, V, W, false>(a.s.partial + (s + u) * (uint64_t)d, gl, d, p[u]);
 #pragma unroll
-            for (int q = 0; q < W; ++q) acc[v][q] = fadd(acc[v][q], p[v][q]);
+            for (int u = 0; u < U - 1; ++u)
+                if ((uint32_t)u < m) {
+#pragma unroll
+                    for (int v = 0; v < V; ++v)
+#pragma unroll
+                        for (int q = 0; q < W; ++q) acc[v][q] = fadd(acc[v][q], p[u][v][q]);
+                }
+        }
     }
 #pragma unroll
     for (int v = 0; v < V; ++v)

@@ -65,6 +65,9 @@ struct RowsF16 {
     static constexpr int G = kG, V = kV, W = C;
     static constexpr int LOADS = C == 4 ? 16 : 8;                     // 128 bytes per lane in flight
     static constexpr int U = (LOADS / V) > 0 ? (LOADS / V) : 1;
+    // every shape whose occupancy the batched tail leaves alone (scripts/kernel_resources.py): not 16 lanes per row with hot marks
+    // (7 -> 6 waves per SIMD)
+    static constexpr bool BATCH_TAIL = !(G == 16 && HOT);
     using row_t = halfs_t<C>[V];
     static_assert(G == 64 || C == 4, "sub-wave groups load 8 bytes per lane");
 
@@ -263,13 +266,22 @@ __global__ __launch_bounds__(256) void hub_finish_h_kernel(const SpmmHArgs a) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc[v][q] = fadd(acc[v][q], p[u][v][q]);
     }
-    for (; s < e; ++s) {
-        float p[V][4];
-        load_row<64, V, 4, false>(a.s.partial + s * (uint64_t)d, gl, d, p);
+    if constexpr (U > 1) {
+        if (s < e) {                                   // the last e - s < U partials: loaded together (spmm_rows.h, BATCH_TAIL), added in order
+            const uint32_t m = (uint32_t)(e - s);
+            float p[U - 1][V][4] = {};
 #pragma unroll
-        for (int v = 0; v < V; ++v)
+            for (int u = 0; u < U - 1; ++u)
+                if ((uint32_t)u < m) load_row<64, V, 4, false>(a.s.partial + (s + u) * (uint64_t)d, gl, d, p[u]);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[v][q] = fadd(acc[v][q], p[v][q]);
+            for (int u = 0; u < U - 1; ++u)
+                if ((uint32_t)u < m) {
+#pragma unroll
+                    for (int v = 0; v < V; ++v)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[v][q] = fadd(acc[v][q], p[u][v][q]);
+                }
+        }
     }
 #pragma unroll
     for (int v = 0; v < V; ++v)

@@ -126,6 +126,7 @@ __device__ __forceinline__ void gather_buffer(const T *x, uint64_t ldx, uint64_t
 // acc += sum over edges [beg, end) in stored order.  For G == 64 beg / end are wave-uniform.  Src is the source policy:
 //   Src::G, V, W           the shape: G lanes per row, V chunks of W columns per lane
 //   Src::U                 rows in flight before the first use
+//   Src::BATCH_TAIL        the row's last cnt % U gathers are issued together (below)
 //   Src::row_t             a gathered row while it is still in registers
 //   Src::gather(a, c, gl, d, r)    gathers row c (bit 31: its hot mark, where the policy has one)
 //   Src::elem(r, v, q)             column q of chunk v of a gathered row as f32; the loop forms acc += w * elem with separate
@@ -157,15 +158,39 @@ __device__ __forceinline__ void accumulate(const Args &a, uint64_t beg, uint64_t
                     for (int q = 0; q < Src::W; ++q) acc[v][q] = fadd(acc[v][q], fmul(w, Src::elem(r[u], v, q)));
             }
         }
-        for (; k < cnt; ++k) {
-            typename Src::row_t r;
-            const uint32_t c = bcast_u32<G>(cv, k, gbase);
-            const float w = bcast_f32<G>(wv, k, gbase);
-            Src::gather(a, c, gl, d, r);
+        // The m = cnt - k < U edges left over.  BATCH_TAIL: one predicated batch — every gather first, then the multiply-adds in
+        // stored order — so a row's tail is one memory round trip, not m.  An absent edge is neither loaded nor added (the zeros only
+        // give every r[u] a definition on every path: left undefined, the rows stayed live across the whole edge loop, +24 VGPRs).
+        // m is wave-uniform at G == 64 (scalar branches); for sub-wave groups it is uniform within a group, so a group's broadcasts
+        // read its own, live lanes.  Without BATCH_TAIL (shapes where the batch cost occupancy) the edges go one by one.
+        if constexpr (Src::BATCH_TAIL && U > 1) {
+            if (k < cnt) {
+                const uint32_t m = cnt - k;
+                typename Src::row_t r[U - 1] = {};
 #pragma unroll
-            for (int v = 0; v < Src::V; ++v)
+                for (int u = 0; u < U - 1; ++u)
+                    if ((uint32_t)u < m) Src::gather(a, bcast_u32<G>(cv, k + u, gbase), gl, d, r[u]);
 #pragma unroll
-                for (int q = 0; q < Src::W; ++q) acc[v][q] = fadd(acc[v][q], fmul(w, Src::elem(r, v, q)));
+                for (int u = 0; u < U - 1; ++u)
+                    if ((uint32_t)u < m) {
+                        const float w = bcast_f32<G>(wv, k + u, gbase);
+#pragma unroll
+                        for (int v = 0; v < Src::V; ++v)
+#pragma unroll
+                            for (int q = 0; q < Src::W; ++q) acc[v][q] = fadd(acc[v][q], fmul(w, Src::elem(r[u], v, q)));
+                    }
+            }
+        } else {
+            for (; k < cnt; ++k) {
+                typename Src::row_t r;
+                const uint32_t c = bcast_u32<G>(cv, k, gbase);
+                const float w = bcast_f32<G>(wv, k, gbase);
+                Src::gather(a, c, gl, d, r);
+#pragma unroll
+                for (int v = 0; v < Src::V; ++v)
+#pragma unroll
+                    for (int q = 0; q < Src::W; ++q) acc[v][q] = fadd(acc[v][q], fmul(w, Src::elem(r, v, q)));
+            }
         }
     }
 }
