@@ -74,6 +74,8 @@ def accelerate(package=None):
         pycleora.whiten_embeddings  -> cleora_amd.embed.whiten_embeddings
         pycleora.embed_multiscale / embed_weighted / embed_directed / embed_with_attention /
         embed_edge_features / predict_links -> cleora_amd.variants.* (same signatures)
+        pycleora.community.detect_communities_kmeans -> cleora_amd.variants.detect_communities_kmeans (when the package
+        object has a `community` attribute with that function; k above the device's cap goes to the original)
     The one normalisation the device path does not run — 'spectral', a full SVD per iteration
     (pycleora/__init__.py:951-956) — is forwarded to the original."""
     import importlib
@@ -97,8 +99,8 @@ def accelerate(package=None):
 
     from . import variants as _var
 
-    def rebind(name):
-        original = getattr(pkg, name, None)
+    def rebind(name, owner=pkg, served=lambda bound: True):
+        original = getattr(owner, name, None)
         device_fn = getattr(_var, name)
         if original is None:
             return
@@ -111,15 +113,19 @@ def accelerate(package=None):
                 return original(*args, **kwargs)
             graph = bound.get("graph")
             if bound.get("normalization", "l2") not in ("l2", "l1", "none") or \
-                    (graph is not None and not isinstance(graph, _dev.SparseMatrix)):
+                    (graph is not None and not isinstance(graph, _dev.SparseMatrix)) or not served(bound):
                 return original(*args, **kwargs)
             return device_fn(*args, **kwargs)
 
         wrapper.__wrapped__ = original
         wrapper.__name__ = name
-        setattr(pkg, name, wrapper)
+        setattr(owner, name, wrapper)
 
     for name in ("embed_multiscale", "embed_weighted", "embed_directed", "embed_with_attention",
                  "embed_edge_features", "predict_links"):
         rebind(name)
+    # pycleora.community.detect_communities_kmeans (pycleora/community.py:5-48) -> the device k-means, up to its cluster cap
+    community = getattr(pkg, "community", None)
+    if community is not None:
+        rebind("detect_communities_kmeans", community, lambda bound: bound["k"] <= _var.KMEANS_MAX_K)
     return pkg

@@ -172,6 +172,10 @@ SIGNATURES = {
     "cleora_topk_cosine_dev": (c_int, [vp, vp, c_u64, c_u64, c_u32, vp, c_u32, c_u32, c_int, c_int, vp, vp, vp, vp]),
     "cleora_knn_workspace": (c_u64, [c_u64, c_u32, c_u32, c_u64]),
     "cleora_knn_cosine_dev": (c_int, [vp, vp, c_u64, c_u64, c_u32, vp, c_u64, c_u32, c_int, c_int, vp, vp, vp, vp]),
+    "cleora_kmeans_workspace": (c_u64, [c_u64, c_u32, c_u32]),
+    "cleora_kmeans_assign_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, vp, vp, vp, vp, vp]),
+    "cleora_kmeans_update_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, vp, c_u32, vp, vp]),
+    "cleora_kmeans_cosine": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, c_u32, vp, ctypes.POINTER(c_u32), vp, vp]),
     "cleora_propagate": (c_int, [vp, c_int, vp, c_u32, vp]),
     "cleora_l2_normalize": (c_int, [vp, c_u64, c_u32, vp]),
     "cleora_init": (c_int, [vp, c_u64, c_u32, c_i64, vp]),

@@ -577,6 +577,23 @@ int cleora_knn_cosine_dev(const cleora_graph *g, const float *x, uint64_t ldx, u
                              out_score_dev, workspace, S(stream));
 }
 
+uint64_t cleora_kmeans_workspace(uint64_t n, uint32_t d, uint32_t k) { return kmeans_workspace_bytes(n, d, k); }
+
+int cleora_kmeans_assign_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *centroids_dev, uint32_t k,
+                             uint32_t *labels_io_dev, float *best_cosine_out_dev, uint64_t *changed_out_dev, void *workspace, void *stream) {
+    return launch_kmeans_assign(x, ldx, n, d, centroids_dev, k, labels_io_dev, best_cosine_out_dev, changed_out_dev, workspace, S(stream));
+}
+
+int cleora_kmeans_update_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint32_t *labels_dev, float *centroids_io_dev,
+                             uint32_t k, void *workspace, void *stream) {
+    return launch_kmeans_update(x, ldx, n, d, labels_dev, centroids_io_dev, k, workspace, S(stream));
+}
+
+int cleora_kmeans_cosine(const float *x_dev, uint64_t ldx, uint64_t n, uint32_t d, float *centroids_io_dev, uint32_t k,
+                         uint32_t max_iterations, uint32_t *labels_out_dev, uint32_t *iterations_out, void *workspace, void *stream) {
+    return kmeans_cosine(x_dev, ldx, n, d, centroids_io_dev, k, max_iterations, labels_out_dev, iterations_out, workspace, S(stream));
+}
+
 uint64_t cleora_gram_workspace(uint64_t n, uint32_t d) { return gram_workspace(n, d); }
 
 int cleora_centered_gram_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d,

@@ -190,6 +190,15 @@ int launch_knn_cosine(const cleora_graph *g, const float *x, uint64_t ldx, uint6
                       uint64_t n_queries, uint32_t k, int exclude_self, int exclude_edges, uint32_t *out_index, float *out_score,
                       void *workspace, hipStream_t stream);
 
+// kmeans.hip: spherical k-means — fused assign (scores on the matrix cores, arg-max in registers) and the order-fixed f64 update
+uint64_t kmeans_workspace_bytes(uint64_t n, uint32_t d, uint32_t k);
+int launch_kmeans_assign(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *centroids, uint32_t k, uint32_t *labels_io,
+                         float *best_cosine_out, uint64_t *changed_out, void *workspace, hipStream_t stream);
+int launch_kmeans_update(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint32_t *labels, float *centroids_io, uint32_t k,
+                         void *workspace, hipStream_t stream);
+int kmeans_cosine(const float *x, uint64_t ldx, uint64_t n, uint32_t d, float *centroids_io, uint32_t k, uint32_t max_iterations,
+                  uint32_t *labels_out, uint32_t *iterations_out, void *workspace, hipStream_t stream);
+
 // stager.hip: pageable host memory <-> device through a pinned ring, at PCIe speed
 int staged_h2d(void *dst_dev, const void *src_host, uint64_t bytes, hipStream_t after);
 int staged_d2h(void *dst_host, const void *src_dev, uint64_t bytes, hipStream_t after);

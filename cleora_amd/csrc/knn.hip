@@ -3,7 +3,8 @@
 // things that leave a block are its queries' k (score, row) pairs.  Same contract as cleora_topk_cosine_dev (similarity.hip),
 // which serves a batch as GEMM -> n x batch scores in HBM -> mask pass over the CSR -> selection passes -> host check.
 //
-//   prepare    knn_inv_norm_kernel: 1 / max(||x_r||, 1e-10) per row (O(n) workspace, padded with zeros to whole tiles);
+//   prepare    knn_inv_norm_kernel (row_inv_norm.h, shared with kmeans.hip): 1 / max(||x_r||, 1e-10) per row (O(n) workspace,
+//              padded with zeros to whole tiles);
 //              knn_pack_kernel: the normalised query rows, [n_queries padded to 64][d padded to 32] (zero padding), and the
 //              row index of every query slot.
 //   block      512 threads = 8 waves own a tile of KQ = 64 queries and walk the candidate rows of their split in tiles of
@@ -39,6 +40,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "row_inv_norm.h"
 
 namespace cleora {
 namespace {
@@ -61,28 +63,6 @@ constexpr uint32_t kNoRow = 0xffffffffu;
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// inv[r] = 1 / max(||x_r||, 1e-10) for r < n, 0 up to n_pad (whole candidate tiles)
-__global__ __launch_bounds__(256) void knn_inv_norm_kernel(const float *__restrict__ x, uint64_t ldx, uint64_t n, uint64_t n_pad,
-                                                           uint32_t d, float *__restrict__ inv) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_pad; row += waves) {
-        float sq = 0.f;
-        if (row < n) {
-            const float *xr = x + row * ldx;
-            for (uint32_t c = lane; c < d; c += 64) sq += xr[c] * xr[c];
-        }
-        sq = wsum(sq);
-        if (lane == 0) inv[row] = row < n ? 1.0f / fmaxf(sqrtf(sq), 1e-10f) : 0.0f;
-    }
-}
 
 // One wave per query slot j: qn[j][0 .. dpad) = x[row_j] / max(||x[row_j]||, 1e-10), zeros beyond d; qrow[j] = row_j.
 // Slots beyond n_queries (the padding of the last tile): a zero row and kNoRow.  A row index >= n is clamped to n - 1.
@@ -404,8 +384,7 @@ int launch_knn_cosine(const cleora_graph *g, const float *x, uint64_t ldx, uint6
     float *part_score = reinterpret_cast<float *>(ws + p.off_part);
     uint32_t *part_index = reinterpret_cast<uint32_t *>(part_score + n_queries * p.splits * k);
 
-    const unsigned grid = (unsigned)((p.n_pad + 3) / 4 < 4096 ? (p.n_pad + 3) / 4 : 4096);
-    hipLaunchKernelGGL(knn_inv_norm_kernel, dim3(grid), dim3(256), 0, stream, x, ldx, n, p.n_pad, d, inv);
+    launch_row_inv_norm(x, ldx, n, p.n_pad, d, inv, stream);
     hipLaunchKernelGGL(knn_pack_kernel, grid_1d_as_2d(p.nq_pad), dim3(64), 0, stream, x, ldx, n, d, p.dpad, queries_dev, n_queries,
                        p.nq_pad, qn, qrow);
     CL_HIP(hipGetLastError());

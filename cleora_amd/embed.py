@@ -317,3 +317,32 @@ def nearest_neighbours(embeddings, k=10, queries=None, graph=None, exclude_self=
     if k > _var.KNN_MAX_K or d > _var.KNN_MAX_D:
         return _var._topk_neighbours(graph, x, np.arange(n) if rows is None else rows, k, bool(exclude_self), bool(exclude_existing))
     return _var._knn_fused(graph, x, rows, k, bool(exclude_self), bool(exclude_existing))
+
+
+def kmeans(embeddings, k, max_iterations=100, seed=42, init=None):
+    """Spherical k-means of the rows (pycleora/community.py:5-48) on the device: (labels int32[n], centroids float32[k, d],
+    iterations).  Every iteration is one fused assign kernel (csrc/kmeans.hip: no n x k score matrix) and the order-fixed f64
+    centroid update; `iterations` counts the assigns, the loop stops at the first one that moves no row.  init None: the
+    reference's start, the normalised rows `np.random.default_rng(seed).choice(n, size=k, replace=False)`, drawn on the host; else
+    a k x d array whose rows are normalised on the host.  One upload, one call of cleora_kmeans_cosine, one download."""
+    from . import variants as _var
+    x = np.ascontiguousarray(embeddings, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("embeddings must be a 2-D array")
+    n, d = x.shape
+    k = int(k)
+    _var._check_kmeans_k(k, n)
+    if init is None:
+        start = x[np.random.default_rng(seed).choice(n, size=k, replace=False)]
+    else:
+        start = np.asarray(init, dtype=np.float32)
+        if start.shape != (k, d):
+            raise ValueError(f"init must have shape ({k}, {d}), got {start.shape}")
+    start = np.ascontiguousarray(start / np.maximum(np.linalg.norm(start, axis=1, keepdims=True), 1e-10), dtype=np.float32)
+    L = _hip.lib()
+    dx, dc = _hip.DevArray.from_host(x), _hip.DevArray.from_host(start)
+    labels = _hip.DevArray((n,), np.uint32)
+    ws = _hip.DevArray((L.cleora_kmeans_workspace(n, d, k),), np.uint8)
+    ran = ctypes.c_uint32(0)
+    _hip.check(L.cleora_kmeans_cosine(dx.ptr, d, n, d, dc.ptr, k, max(int(max_iterations), 0), labels.ptr, ctypes.byref(ran), ws.ptr, None))
+    return labels.to_host().astype(np.int32), dc.to_host(), int(ran.value)

@@ -288,3 +288,24 @@ def _topk_neighbours(graph, x, query_rows, k, exclude_self, exclude_existing):
                                             1 if exclude_existing else 0, oi.ptr, os_.ptr, ws.ptr, None))
         _hip.check(L.cleora_stream_sync(None))
     return oi.to_host(), os_.to_host()
+
+
+KMEANS_MAX_K = 4096         # CLEORA_KMEANS_MAX_K: the most clusters the device k-means takes (csrc/kmeans.hip)
+
+
+def _check_kmeans_k(k, n):
+    if k < 2:                                                            # pycleora/community.py:13-16
+        raise ValueError("k must be at least 2")
+    if k > n:
+        raise ValueError(f"k ({k}) cannot be larger than number of entities ({n})")
+    if k > KMEANS_MAX_K:
+        raise ValueError(f"k ({k}) is larger than CLEORA_KMEANS_MAX_K = {KMEANS_MAX_K}, the most clusters the device k-means takes")
+
+
+def detect_communities_kmeans(graph, embeddings, k, max_iterations=100, seed=42):
+    """(pycleora/community.py:5-48).  Spherical k-means of the embedding from the reference's seeded start, on the device
+    (embed.kmeans): {entity_id: cluster}."""
+    from .embed import kmeans
+    _check_kmeans_k(int(k), np.shape(embeddings)[0])
+    labels, _, _ = kmeans(embeddings, k, max_iterations=max_iterations, seed=seed)
+    return {eid: int(labels[i]) for i, eid in enumerate(graph.entity_ids)}

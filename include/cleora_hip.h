@@ -664,6 +664,37 @@ int cleora_knn_cosine_dev(const cleora_graph *g, const float *x, uint64_t ldx, u
                           const uint32_t *query_rows_dev, uint64_t n_queries, uint32_t k, int exclude_self,
                           int exclude_existing, uint32_t *out_index_dev, float *out_score_dev, void *workspace, void *stream);
 
+/* Spherical k-means of an embedding (pycleora/community.py:5-48, detect_communities_kmeans) on the device (csrc/kmeans.hip).
+ *   assign: label[r] = argmax_c x[r] . centroid[c] over k UNIT centroid rows (k x d, dense), ties to the lower centroid index
+ *   (numpy's argmax); an all-zero row takes label 0.  One fused kernel: a block keeps 64 rows of X in LDS (d <= 256; wider rows are
+ *   re-staged in 32-column chunks), every centroid streams past them on the f32 matrix cores and the arg-max stays in registers — no
+ *   n x k score matrix.  labels_io_dev: u32[n], the previous labels on entry, the new ones on return; *changed_out_dev (u64): how
+ *   many differ; best_cosine_out_dev (f32[n] or NULL): the winner's score / max(||x[r]||, 1e-10).
+ *   update (:36-42): centroid[c] = the mean over the members of x[r] / max(||x[r]||, 1e-10), divided by its norm when that is above
+ *   1e-10; otherwise, and for a cluster without members, the old centroid stays bit for bit.  Sums are f64 in an order fixed by
+ *   (labels, n, k, d): the members of a cluster in ascending row order, in chunks of 256, the chunks in order; one rounding to f32.
+ *   Labels >= k belong to no cluster.
+ *   Same input, same output bits; no floating-point atomics.  Rows containing NaN or Inf: unspecified.
+ *   Limits: 2 <= k <= min(n, CLEORA_KMEANS_MAX_K), n < 2^32, 1 <= d <= 16384, ldx >= d, no NULL pointer (best_cosine_out_dev
+ *   excepted); anything else returns CLEORA_E_INVALID before any device work.  CLEORA_KMEANS_MAX_K is bounded by the update: one
+ *   wave per row segment keeps a u32 counter per cluster in LDS (16 KiB at 4096, several such blocks per CU) and the
+ *   segment x cluster table stays at 8 MiB.
+ *   workspace: cleora_kmeans_workspace(n, d, k) BYTES — 1 / ||x_r||, the padded centroids, the member lists, the segment table and
+ *   the f64 chunk partials ((n / 256 + k) x d doubles); monotone in every argument, plain host arithmetic.  One workspace serves
+ *   all three entry points, one call at a time.
+ * The two *_dev entry points only enqueue on `stream`.  cleora_kmeans_cosine is the reference's loop and SYNCHRONISES (hence no
+ * _dev suffix): labels start at 0; every iteration assigns, waits for the stream to read the 8-byte changed count, stops when it is
+ * 0 and updates otherwise; at most max_iterations assigns, *iterations_out (HOST) = how many ran.  It returns when labels_out_dev
+ * and centroids_io_dev are in place. */
+#define CLEORA_KMEANS_MAX_K 4096
+uint64_t cleora_kmeans_workspace(uint64_t n, uint32_t d, uint32_t k);
+int cleora_kmeans_assign_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *centroids_dev, uint32_t k,
+                             uint32_t *labels_io_dev, float *best_cosine_out_dev, uint64_t *changed_out_dev, void *workspace, void *stream);
+int cleora_kmeans_update_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint32_t *labels_dev, float *centroids_io_dev,
+                             uint32_t k, void *workspace, void *stream);
+int cleora_kmeans_cosine(const float *x_dev, uint64_t ldx, uint64_t n, uint32_t d, float *centroids_io_dev, uint32_t k,
+                         uint32_t max_iterations, uint32_t *labels_out_dev, uint32_t *iterations_out, void *workspace, void *stream);
+
 /* ---- host-pointer entry points: what the PyO3 methods call ------------------------- */
 
 /* SparseMatrix::markov_propagate → NdArrayMatrix::multiply (src/lib.rs:29-47, src/embedding.rs:15-39).
