@@ -4,6 +4,7 @@
   cleora_amd.embed                   device-resident embed()/whitening loop (pycleora/__init__.py:51-164)
   cleora_amd.variants                device-resident embed variants + predict_links (pycleora/__init__.py:206-410, 636-681, 784-852)
   cleora_amd.sharded                 column- / row-partitioned multi-GPU propagation (one process per GPU)
+  cleora_amd.compress                product quantisation on the device: product_quantize / PQIndex (pycleora/compress.py:32-181)
   cleora_amd._hip                    ctypes binding of libcleora_hip.so (include/cleora_hip.h)
 """
 __version__ = "0.1.0"
@@ -76,6 +77,8 @@ def accelerate(package=None):
         embed_edge_features / predict_links -> cleora_amd.variants.* (same signatures)
         pycleora.community.detect_communities_kmeans -> cleora_amd.variants.detect_communities_kmeans (when the package
         object has a `community` attribute with that function; k above the device's cap goes to the original)
+        pycleora.compress.product_quantize -> cleora_amd.compress.product_quantize (when the package object has a `compress`
+        attribute with that function; shapes beyond the device's limits go to the original)
     The one normalisation the device path does not run — 'spectral', a full SVD per iteration
     (pycleora/__init__.py:951-956) — is forwarded to the original."""
     import importlib
@@ -128,4 +131,24 @@ def accelerate(package=None):
     community = getattr(pkg, "community", None)
     if community is not None:
         rebind("detect_communities_kmeans", community, lambda bound: bound["k"] <= _var.KMEANS_MAX_K)
+    # pycleora.compress.product_quantize (pycleora/compress.py:101-181) -> the device product quantisation, within its limits
+    compress = getattr(pkg, "compress", None)
+    original_pq = getattr(compress, "product_quantize", None)
+    if original_pq is not None:
+        from . import compress as _pq
+        sig = inspect.signature(_pq.product_quantize)
+
+        def product_quantize(*args, **kwargs):
+            try:
+                bound = sig.bind(*args, **kwargs)
+                bound.apply_defaults()
+                shape = getattr(bound.arguments["embeddings"], "shape", ())
+                M, kc = bound.arguments["num_subspaces"], bound.arguments["num_centroids"]
+                served = len(shape) == 2 and M > 0 and shape[1] % M == 0 and _pq._device_serves(shape[0], M, kc, shape[1] // M)
+            except TypeError:
+                served = False
+            return _pq.product_quantize(*args, **kwargs) if served else original_pq(*args, **kwargs)
+
+        product_quantize.__wrapped__ = original_pq
+        compress.product_quantize = product_quantize
     return pkg

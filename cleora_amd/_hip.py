@@ -176,6 +176,13 @@ SIGNATURES = {
     "cleora_kmeans_assign_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, vp, vp, vp, vp, vp]),
     "cleora_kmeans_update_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, vp, c_u32, vp, vp]),
     "cleora_kmeans_cosine": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, c_u32, vp, ctypes.POINTER(c_u32), vp, vp]),
+    "cleora_pq_workspace": (c_u64, [c_u64, c_u32, c_u32, c_u32]),
+    "cleora_pq_assign_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, c_u32, vp, vp, vp, vp]),
+    "cleora_pq_update_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, vp, c_u32, c_u32, vp, vp, vp]),
+    "cleora_pq_train": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, c_u32, c_u32, vp, ctypes.POINTER(c_u32), vp, vp]),
+    "cleora_pq_search_workspace": (c_u64, [c_u64, c_u32, c_u32, c_u64, c_u32]),
+    "cleora_pq_search_dev": (c_int, [vp, c_u64, vp, c_u32, c_u32, c_u32, vp, c_u64, c_u32, vp, vp, vp, vp, vp]),
+    "cleora_pq_reconstruct_dev": (c_int, [vp, c_u64, vp, c_u32, c_u32, c_u32, vp, c_u64, vp, c_u64, vp]),
     "cleora_propagate": (c_int, [vp, c_int, vp, c_u32, vp]),
     "cleora_l2_normalize": (c_int, [vp, c_u64, c_u32, vp]),
     "cleora_init": (c_int, [vp, c_u64, c_u32, c_i64, vp]),

@@ -594,6 +594,43 @@ int cleora_kmeans_cosine(const float *x_dev, uint64_t ldx, uint64_t n, uint32_t 
     return kmeans_cosine(x_dev, ldx, n, d, centroids_io_dev, k, max_iterations, labels_out_dev, iterations_out, workspace, S(stream));
 }
 
+uint64_t cleora_pq_workspace(uint64_t n, uint32_t d, uint32_t n_subspaces, uint32_t n_centroids) {
+    return pq_workspace_bytes(n, d, n_subspaces, n_centroids);
+}
+
+int cleora_pq_assign_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *codebooks_dev, uint32_t n_subspaces,
+                         uint32_t n_centroids, uint8_t *codes_out_dev, float *sqdist_out_dev, void *workspace, void *stream) {
+    return launch_pq_assign(x, ldx, n, d, codebooks_dev, n_subspaces, n_centroids, codes_out_dev, sqdist_out_dev, workspace, S(stream));
+}
+
+int cleora_pq_update_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint8_t *codes_dev, float *codebooks_io_dev,
+                         uint32_t n_subspaces, uint32_t n_centroids, uint32_t *close_out_dev, void *workspace, void *stream) {
+    return launch_pq_update(x, ldx, n, d, codes_dev, codebooks_io_dev, n_subspaces, n_centroids, close_out_dev, workspace, S(stream));
+}
+
+int cleora_pq_train(const float *x_dev, uint64_t ldx, uint64_t n, uint32_t d, float *codebooks_io_dev, uint32_t n_subspaces,
+                    uint32_t n_centroids, uint32_t max_iterations, uint8_t *codes_out_dev, uint32_t *iterations_out, void *workspace,
+                    void *stream) {
+    return pq_train(x_dev, ldx, n, d, codebooks_io_dev, n_subspaces, n_centroids, max_iterations, codes_out_dev, iterations_out, workspace,
+                    S(stream));
+}
+
+uint64_t cleora_pq_search_workspace(uint64_t n, uint32_t n_subspaces, uint32_t n_centroids, uint64_t n_queries, uint32_t top_k) {
+    return pq_search_workspace_bytes(n, n_subspaces, n_centroids, n_queries, top_k);
+}
+
+int cleora_pq_search_dev(const uint8_t *codes_dev, uint64_t n, const float *codebooks_dev, uint32_t n_subspaces, uint32_t n_centroids,
+                         uint32_t subspace_dim, const float *queries_dev, uint64_t n_queries, uint32_t top_k, uint32_t *out_index_dev,
+                         float *out_score_dev, float *all_scores_out_dev, void *workspace, void *stream) {
+    return launch_pq_search(codes_dev, n, codebooks_dev, n_subspaces, n_centroids, subspace_dim, queries_dev, n_queries, top_k, out_index_dev,
+                            out_score_dev, all_scores_out_dev, workspace, S(stream));
+}
+
+int cleora_pq_reconstruct_dev(const uint8_t *codes_dev, uint64_t n, const float *codebooks_dev, uint32_t n_subspaces, uint32_t n_centroids,
+                              uint32_t subspace_dim, const uint32_t *rows_dev, uint64_t n_rows, float *out_dev, uint64_t ldo, void *stream) {
+    return launch_pq_reconstruct(codes_dev, n, codebooks_dev, n_subspaces, n_centroids, subspace_dim, rows_dev, n_rows, out_dev, ldo, S(stream));
+}
+
 uint64_t cleora_gram_workspace(uint64_t n, uint32_t d) { return gram_workspace(n, d); }
 
 int cleora_centered_gram_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d,

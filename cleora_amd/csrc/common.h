@@ -199,6 +199,21 @@ int launch_kmeans_update(const float *x, uint64_t ldx, uint64_t n, uint32_t d, c
 int kmeans_cosine(const float *x, uint64_t ldx, uint64_t n, uint32_t d, float *centroids_io, uint32_t k, uint32_t max_iterations,
                   uint32_t *labels_out, uint32_t *iterations_out, void *workspace, hipStream_t stream);
 
+// pq.hip: product quantisation — fused encode for all subspaces, the order-fixed Euclidean update, the loop, batched ADC search
+uint64_t pq_workspace_bytes(uint64_t n, uint32_t d, uint32_t M, uint32_t kc);
+int launch_pq_assign(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *codebooks, uint32_t M, uint32_t kc, uint8_t *codes_out,
+                     float *sqdist_out, void *workspace, hipStream_t stream);
+int launch_pq_update(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint8_t *codes, float *codebooks_io, uint32_t M, uint32_t kc,
+                     uint32_t *close_out, void *workspace, hipStream_t stream);
+int pq_train(const float *x, uint64_t ldx, uint64_t n, uint32_t d, float *codebooks_io, uint32_t M, uint32_t kc, uint32_t max_iterations,
+             uint8_t *codes_out, uint32_t *iterations_out, void *workspace, hipStream_t stream);
+uint64_t pq_search_workspace_bytes(uint64_t n, uint32_t M, uint32_t kc, uint64_t nq, uint32_t top_k);
+int launch_pq_search(const uint8_t *codes, uint64_t n, const float *codebooks, uint32_t M, uint32_t kc, uint32_t ds, const float *queries,
+                     uint64_t nq, uint32_t top_k, uint32_t *out_index, float *out_score, float *all_scores_out, void *workspace,
+                     hipStream_t stream);
+int launch_pq_reconstruct(const uint8_t *codes, uint64_t n, const float *codebooks, uint32_t M, uint32_t kc, uint32_t ds, const uint32_t *rows,
+                          uint64_t n_rows, float *out, uint64_t ldo, hipStream_t stream);
+
 // stager.hip: pageable host memory <-> device through a pinned ring, at PCIe speed
 int staged_h2d(void *dst_dev, const void *src_host, uint64_t bytes, hipStream_t after);
 int staged_d2h(void *dst_host, const void *src_dev, uint64_t bytes, hipStream_t after);

@@ -291,6 +291,11 @@ def _topk_neighbours(graph, x, query_rows, k, exclude_self, exclude_existing):
 
 
 KMEANS_MAX_K = 4096         # CLEORA_KMEANS_MAX_K: the most clusters the device k-means takes (csrc/kmeans.hip)
+# what the device product quantisation takes (csrc/pq.hip); anything beyond goes to the numpy statement in compress.py
+PQ_MAX_CENTROIDS = 256      # per subspace: codes are uint8 (and never more than rows)
+PQ_MAX_SUBSPACE_DIM = 64    # columns per subspace: the codebook stays resident in LDS
+PQ_MAX_SUBSPACES = 64
+PQ_MAX_TOP_K = 32           # the scan's list per query
 
 
 def _check_kmeans_k(k, n):

@@ -695,6 +695,49 @@ int cleora_kmeans_update_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t 
 int cleora_kmeans_cosine(const float *x_dev, uint64_t ldx, uint64_t n, uint32_t d, float *centroids_io_dev, uint32_t k,
                          uint32_t max_iterations, uint32_t *labels_out_dev, uint32_t *iterations_out, void *workspace, void *stream);
 
+/* Product quantisation of an embedding (pycleora/compress.py:32-181, product_quantize / PQIndex) on the device (csrc/pq.hip).  The d
+ * columns are cut into n_subspaces slices of d / n_subspaces columns; every slice has its own codebook of n_centroids centroids
+ * (codebooks: [n_subspaces][n_centroids][d / n_subspaces] floats, dense) and a row is stored as one byte per slice (codes:
+ * u8[n][n_subspaces], dense).
+ *   assign: codes[r][m] = argmin_c ||c||^2 - 2 x_rm . c, ties to the lower index (numpy's argmin).  One launch for all subspaces; a
+ *   block keeps its subspace's whole codebook in LDS and streams the rows past it on the f32 matrix cores with the arg-min in
+ *   registers — no n x n_centroids distances.  sqdist_out_dev (f32[n][n_subspaces] or NULL): ||x_rm - c||^2 of the chosen centroid.
+ *   update: every centroid becomes the mean of its members' slices — f64 sums in ascending row order, chunks of 256, one rounding to
+ *   f32; a centroid without members keeps its bits.  close_out_dev (u32[n_subspaces]): 1 where |old - new| <= 1e-6 + 1e-5 |new| holds
+ *   for every element of the subspace's codebook, evaluated in f32 as np.allclose(old, new, atol=1e-6) does.  Codes >= n_centroids
+ *   belong to no centroid.
+ *   cleora_pq_train is the reference's loop for all subspaces together and SYNCHRONISES: up to max_iterations x (assign, update,
+ *   a read-back of n_subspaces flags); a subspace that passed the allclose test is frozen (never updated again); the loop ends when
+ *   all are frozen; a last assign writes codes_out_dev.  *iterations_out (HOST): the updates that ran.
+ *   search (ADC): table[q][m][c] = c_mc / max(||c_mc||, 1e-10) . q_m / ||q|| (q unscaled when ||q|| <= 1e-10; f64, rounded once);
+ *   score[q][r] = the n_subspaces table values of row r's codes added in subspace order in f32, starting from +0.  Output
+ *   [n_queries][top_k], score descending, ties to the larger row index; the selection happens inside the scan kernel, few query
+ *   tiles split the rows over up to 512 blocks and a second kernel merges.  all_scores_out_dev (f32[n_queries][n] or NULL): every
+ *   score, for tests.  queries_dev: [n_queries][d] floats, dense.
+ *   reconstruct: out[i][m ds + j] = codebooks[m][codes[row][m]][j], row = rows_dev[i] (NULL: i); rows >= n and codes >= n_centroids
+ *   give zeros.
+ *   Same input, same output bits; no floating-point atomics.  NaN or Inf anywhere: unspecified.
+ *   Limits: d % n_subspaces == 0, 1 <= d / n_subspaces <= 64, 1 <= n_subspaces <= 64, 1 <= n_centroids <= min(n, 256), n < 2^32,
+ *   ldx >= d, 1 <= top_k <= min(n, 32), 1 <= n_queries <= 2^22; update and train also n * n_subspaces < 2^32; no NULL pointer
+ *   (the optional outputs excepted).  Anything else returns CLEORA_E_INVALID before any device work.
+ *   workspace: cleora_pq_workspace BYTES serve assign, update and train (code planes, member lists, segment table, f64 chunk
+ *   partials); cleora_pq_search_workspace BYTES the tables and the split lists.  Monotone, plain host arithmetic.
+ * The *_dev entry points only enqueue on `stream`. */
+uint64_t cleora_pq_workspace(uint64_t n, uint32_t d, uint32_t n_subspaces, uint32_t n_centroids);
+int cleora_pq_assign_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const float *codebooks_dev, uint32_t n_subspaces,
+                         uint32_t n_centroids, uint8_t *codes_out_dev, float *sqdist_out_dev, void *workspace, void *stream);
+int cleora_pq_update_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint8_t *codes_dev, float *codebooks_io_dev,
+                         uint32_t n_subspaces, uint32_t n_centroids, uint32_t *close_out_dev, void *workspace, void *stream);
+int cleora_pq_train(const float *x_dev, uint64_t ldx, uint64_t n, uint32_t d, float *codebooks_io_dev, uint32_t n_subspaces,
+                    uint32_t n_centroids, uint32_t max_iterations, uint8_t *codes_out_dev, uint32_t *iterations_out, void *workspace,
+                    void *stream);
+uint64_t cleora_pq_search_workspace(uint64_t n, uint32_t n_subspaces, uint32_t n_centroids, uint64_t n_queries, uint32_t top_k);
+int cleora_pq_search_dev(const uint8_t *codes_dev, uint64_t n, const float *codebooks_dev, uint32_t n_subspaces, uint32_t n_centroids,
+                         uint32_t subspace_dim, const float *queries_dev, uint64_t n_queries, uint32_t top_k, uint32_t *out_index_dev,
+                         float *out_score_dev, float *all_scores_out_dev, void *workspace, void *stream);
+int cleora_pq_reconstruct_dev(const uint8_t *codes_dev, uint64_t n, const float *codebooks_dev, uint32_t n_subspaces, uint32_t n_centroids,
+                              uint32_t subspace_dim, const uint32_t *rows_dev, uint64_t n_rows, float *out_dev, uint64_t ldo, void *stream);
+
 /* ---- host-pointer entry points: what the PyO3 methods call ------------------------- */
 
 /* SparseMatrix::markov_propagate → NdArrayMatrix::multiply (src/lib.rs:29-47, src/embedding.rs:15-39).
