@@ -5,6 +5,7 @@
   cleora_amd.variants                device-resident embed variants + predict_links (pycleora/__init__.py:206-410, 636-681, 784-852)
   cleora_amd.sharded                 column- / row-partitioned multi-GPU propagation (one process per GPU)
   cleora_amd.compress                product quantisation on the device: product_quantize / PQIndex (pycleora/compress.py:32-181)
+  cleora_amd.search                  approximate nearest neighbours on the device: IVFIndex / ANNIndex (pycleora/search.py:101-215)
   cleora_amd._hip                    ctypes binding of libcleora_hip.so (include/cleora_hip.h)
 """
 __version__ = "0.1.0"

@@ -176,6 +176,12 @@ SIGNATURES = {
     "cleora_kmeans_assign_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, vp, vp, vp, vp, vp]),
     "cleora_kmeans_update_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, vp, c_u32, vp, vp]),
     "cleora_kmeans_cosine": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, c_u32, vp, ctypes.POINTER(c_u32), vp, vp]),
+    "cleora_ivf_xs_bytes": (c_u64, [c_u64, c_u32, c_u32]),
+    "cleora_ivf_build_workspace": (c_u64, [c_u64, c_u32]),
+    "cleora_ivf_build_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, vp, vp, vp, vp, vp]),
+    "cleora_ivf_search_workspace": (c_u64, [c_u64, c_u32, c_u32, c_u32, c_u32, c_u64]),
+    "cleora_ivf_search_dev": (c_int, [vp, vp, vp, vp, c_u64, c_u64, c_u32, vp, c_u32, vp, vp, c_u64, c_u32, c_u32, c_int, vp, vp, vp, vp,
+                                      c_u64, vp]),
     "cleora_pq_workspace": (c_u64, [c_u64, c_u32, c_u32, c_u32]),
     "cleora_pq_assign_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, c_u32, c_u32, vp, vp, vp, vp]),
     "cleora_pq_update_dev": (c_int, [vp, c_u64, c_u64, c_u32, vp, vp, c_u32, c_u32, vp, vp, vp]),

@@ -594,6 +594,28 @@ int cleora_kmeans_cosine(const float *x_dev, uint64_t ldx, uint64_t n, uint32_t 
     return kmeans_cosine(x_dev, ldx, n, d, centroids_io_dev, k, max_iterations, labels_out_dev, iterations_out, workspace, S(stream));
 }
 
+uint64_t cleora_ivf_xs_bytes(uint64_t n, uint32_t d, uint32_t nlist) { return ivf_xs_bytes(n, d, nlist); }
+
+uint64_t cleora_ivf_build_workspace(uint64_t n, uint32_t nlist) { return ivf_build_workspace_bytes(n, nlist); }
+
+int cleora_ivf_build_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint32_t *labels_dev, uint32_t nlist,
+                         uint64_t *list_ptr_out_dev, uint32_t *list_rows_out_dev, float *xs_out_dev, void *workspace, void *stream) {
+    return launch_ivf_build(x, ldx, n, d, labels_dev, nlist, list_ptr_out_dev, list_rows_out_dev, xs_out_dev, workspace, S(stream));
+}
+
+uint64_t cleora_ivf_search_workspace(uint64_t n, uint32_t d, uint32_t nlist, uint32_t nprobe, uint32_t k, uint64_t n_queries) {
+    return ivf_search_workspace_bytes(n, d, nlist, nprobe, k, n_queries);
+}
+
+int cleora_ivf_search_dev(const uint64_t *list_ptr_dev, const uint32_t *list_rows_dev, const float *xs_dev, const float *x, uint64_t ldx,
+                          uint64_t n, uint32_t d, const float *centroids_dev, uint32_t nlist, const float *queries_dev,
+                          const uint32_t *query_rows_dev, uint64_t n_queries, uint32_t nprobe, uint32_t k, int exclude_self,
+                          uint32_t *out_index_dev, float *out_score_dev, uint32_t *probes_out_dev, void *workspace,
+                          uint64_t workspace_queries, void *stream) {
+    return launch_ivf_search(list_ptr_dev, list_rows_dev, xs_dev, x, ldx, n, d, centroids_dev, nlist, queries_dev, query_rows_dev, n_queries,
+                             nprobe, k, exclude_self, out_index_dev, out_score_dev, probes_out_dev, workspace, workspace_queries, S(stream));
+}
+
 uint64_t cleora_pq_workspace(uint64_t n, uint32_t d, uint32_t n_subspaces, uint32_t n_centroids) {
     return pq_workspace_bytes(n, d, n_subspaces, n_centroids);
 }

@@ -189,6 +189,31 @@ uint64_t knn_workspace_bytes(uint64_t n, uint32_t d, uint32_t k, uint64_t n_quer
 int launch_knn_cosine(const cleora_graph *g, const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint32_t *queries_dev,
                       uint64_t n_queries, uint32_t k, int exclude_self, int exclude_edges, uint32_t *out_index, float *out_score,
                       void *workspace, hipStream_t stream);
+// ... and its two halves for a caller with queries of its own (ivf.hip: the centroids as candidates): the packed-query slots of a
+// workspace of knn_workspace_bytes(n, d, k, n_queries), the pack of rows_dev-indexed rows of src (rows_dev == nullptr: src holds
+// n_queries dense query rows), and the scan + merge over queries already packed there
+struct KnnSlots {
+    float *qn;          // [nq_pad][dpad] normalised, zero-padded
+    uint32_t *qrow;     // [nq_pad] row index of the slot, 0xffffffff = padding
+    uint32_t dpad;
+    uint64_t nq_pad;
+};
+KnnSlots knn_query_slots(void *workspace, uint64_t n, uint32_t d, uint32_t k, uint64_t n_queries);
+int launch_knn_pack(const float *src, uint64_t lds, uint64_t n_src, uint32_t d, const uint32_t *rows_dev, uint64_t n_queries,
+                    const KnnSlots &slots, hipStream_t stream);
+int launch_knn_packed(const cleora_graph *g, const float *x, uint64_t ldx, uint64_t n, uint32_t d, uint64_t n_queries, uint32_t k,
+                      int exclude_self, int exclude_edges, uint32_t *out_index, float *out_score, void *workspace, hipStream_t stream);
+
+// ivf.hip: inverted-file index — the list layout and the grouped list-scan search
+uint64_t ivf_xs_bytes(uint64_t n, uint32_t d, uint32_t nlist);
+uint64_t ivf_build_workspace_bytes(uint64_t n, uint32_t nlist);
+int launch_ivf_build(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint32_t *labels, uint32_t nlist, uint64_t *list_ptr,
+                     uint32_t *list_rows, float *xs, void *workspace, hipStream_t stream);
+uint64_t ivf_search_workspace_bytes(uint64_t n, uint32_t d, uint32_t nlist, uint32_t nprobe, uint32_t k, uint64_t n_queries);
+int launch_ivf_search(const uint64_t *list_ptr, const uint32_t *list_rows, const float *xs, const float *x, uint64_t ldx, uint64_t n,
+                      uint32_t d, const float *centroids, uint32_t nlist, const float *queries, const uint32_t *query_rows,
+                      uint64_t n_queries, uint32_t nprobe, uint32_t k, int exclude_self, uint32_t *out_index, float *out_score,
+                      uint32_t *probes_out, void *workspace, uint64_t workspace_queries, hipStream_t stream);
 
 // kmeans.hip: spherical k-means — fused assign (scores on the matrix cores, arg-max in registers) and the order-fixed f64 update
 uint64_t kmeans_workspace_bytes(uint64_t n, uint32_t d, uint32_t k);

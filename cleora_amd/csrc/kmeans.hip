@@ -24,7 +24,7 @@
 //              integer atomic per block.  X is not normalised for the arg-max: ||x_r|| > 0 scales a row's scores alike, a zero row
 //              scores 0 everywhere and takes label 0.
 //   update     centroid_c = normalise(mean over members of x_r / max(||x_r||, 1e-10)), in f64, in an order that depends only on
-//              (labels, n, k, d):
+//              (labels, n, k, d); count, scan and place are member_lists.h (shared with ivf.hip):
 //     count    the rows are cut into at most 512 segments of consecutive rows; one wave per segment counts its labels in LDS
 //              (integer atomics) -> table[segment][cluster];
 //     scan     per cluster over the segments (exclusive, in place), then over the clusters: coff[c] = first member slot of
@@ -40,6 +40,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "member_lists.h"
 #include "row_inv_norm.h"
 
 namespace cleora {
@@ -55,8 +56,6 @@ constexpr uint32_t kKmeansMaxD = 16384;
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t UCHUNK = 256;          // members per chunk of the update's sum
 constexpr uint32_t USLAB = 256;           // columns per slab = threads per block of the sum
-constexpr uint64_t USEGS = 512;           // most row segments of count / place
-constexpr uint64_t USEG_MIN_ROWS = 1024;  // fewest rows per segment (a multiple of 64)
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -236,107 +235,6 @@ __global__ __launch_bounds__(256) void kmeans_fill_kernel(uint32_t *__restrict__
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) v[i] = value;
 }
 
-// One wave per segment of consecutive rows: table[segment][c] = rows of the segment with label c.
-__global__ __launch_bounds__(64) void kmeans_count_kernel(const uint32_t *__restrict__ labels, uint64_t n, uint64_t seg_rows, uint32_t k,
-                                                          uint32_t *__restrict__ table) {
-    extern __shared__ uint32_t kmeans_cnt[];
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t c = lane; c < k; c += 64) kmeans_cnt[c] = 0;
-    __syncthreads();
-    const uint64_t begin = (uint64_t)blockIdx.x * seg_rows, end = begin + seg_rows < n ? begin + seg_rows : n;
-    for (uint64_t r = begin + lane; r < end; r += 64) {
-        const uint32_t l = labels[r];
-        if (l < k) atomicAdd(&kmeans_cnt[l], 1u);
-    }
-    __syncthreads();
-    for (uint32_t c = lane; c < k; c += 64) table[(uint64_t)blockIdx.x * k + c] = kmeans_cnt[c];
-}
-
-// One thread per cluster: its column of the table becomes the exclusive scan over the segments; count[c] = its total.
-__global__ __launch_bounds__(256) void kmeans_segscan_kernel(uint32_t *__restrict__ table, uint32_t segs, uint32_t k, uint32_t *__restrict__ count) {
-    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= k) return;
-    uint32_t run = 0;
-    for (uint32_t b = 0; b < segs; b += 8) {
-        uint32_t v[8];
-#pragma unroll
-        for (uint32_t u = 0; u < 8; ++u) v[u] = b + u < segs ? table[(uint64_t)(b + u) * k + c] : 0u;
-#pragma unroll
-        for (uint32_t u = 0; u < 8; ++u)
-            if (b + u < segs) {
-                table[(uint64_t)(b + u) * k + c] = run;
-                run += v[u];
-            }
-    }
-    count[c] = run;
-}
-
-// One block: coff[c] = members before cluster c, choff[c] = chunks of UCHUNK members before it; [k] = the totals.
-__global__ __launch_bounds__(256) void kmeans_offsets_kernel(const uint32_t *__restrict__ count, uint32_t k, uint32_t *__restrict__ coff,
-                                                             uint32_t *__restrict__ choff) {
-    __shared__ uint32_t sa[256], sb[256];
-    const uint32_t t = threadIdx.x, per = (k + 255) / 256;
-    const uint32_t c0 = t * per, c1 = c0 + per < k ? c0 + per : k;
-    uint32_t ma = 0, mb = 0;
-    for (uint32_t c = c0; c < c1; ++c) {
-        ma += count[c];
-        mb += (count[c] + UCHUNK - 1) / UCHUNK;
-    }
-    sa[t] = ma;
-    sb[t] = mb;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {
-        const uint32_t va = t >= o ? sa[t - o] : 0u, vb = t >= o ? sb[t - o] : 0u;
-        __syncthreads();
-        sa[t] += va;
-        sb[t] += vb;
-        __syncthreads();
-    }
-    uint32_t ra = sa[t] - ma, rb = sb[t] - mb;
-    for (uint32_t c = c0; c < c1; ++c) {
-        coff[c] = ra;
-        choff[c] = rb;
-        ra += count[c];
-        rb += (count[c] + UCHUNK - 1) / UCHUNK;
-    }
-    if (t == 255) {
-        coff[k] = sa[255];
-        choff[k] = sb[255];
-    }
-}
-
-// One wave per segment, 64 rows at a time in row order: members[coff[c] ..] = the rows of cluster c, ascending.
-__global__ __launch_bounds__(64) void kmeans_place_kernel(const uint32_t *__restrict__ labels, uint64_t n, uint64_t seg_rows, uint32_t k,
-                                                          const uint32_t *__restrict__ table, const uint32_t *__restrict__ coff,
-                                                          uint32_t *__restrict__ members) {
-    extern __shared__ uint32_t kmeans_cur[];
-    const int lane = threadIdx.x;
-    for (uint32_t c = lane; c < k; c += 64) kmeans_cur[c] = coff[c] + table[(uint64_t)blockIdx.x * k + c];
-    __syncthreads();
-    const uint64_t begin = (uint64_t)blockIdx.x * seg_rows, end = begin + seg_rows < n ? begin + seg_rows : n;
-    for (uint64_t base = begin; base < end; base += 64) {
-        const uint64_t r = base + lane;
-        uint32_t l = r < end ? labels[r] : kNone;
-        if (l >= k) l = kNone;
-        uint32_t before = 0;
-        bool later = false;
-#pragma unroll
-        for (int j = 0; j < 64; ++j) {
-            const bool same = (uint32_t)__shfl((int)l, j, 64) == l;
-            before += (same && j < lane) ? 1u : 0u;
-            later = later || (same && j > lane);
-        }
-        uint32_t pos = 0;
-        if (l != kNone) {
-            pos = kmeans_cur[l] + before;
-            if (pos < n) members[pos] = (uint32_t)r;      // always true while nobody rewrites the labels under this call
-        }
-        __syncthreads();
-        if (l != kNone && !later) kmeans_cur[l] = pos + 1;    // the last lane of a label moves its cursor
-        __syncthreads();
-    }
-}
-
 // One block per (chunk, column slab): part[chunk][col] = sum over the chunk's members, in member order, of x[m][col] / ||x_m|| (f64).
 __global__ __launch_bounds__(USLAB) void kmeans_sum_kernel(const float *__restrict__ x, uint64_t ldx, uint32_t d, const float *__restrict__ inv,
                                                            const uint32_t *__restrict__ members, const uint32_t *__restrict__ coff,
@@ -399,8 +297,8 @@ __global__ __launch_bounds__(256) void kmeans_finish_kernel(double *__restrict__
 // ---------------------------------------------------------------------------------------------------------------- host
 
 struct KmeansPlan {
-    uint32_t dpad, kpad, segs;
-    uint64_t seg_rows, max_chunks;
+    uint32_t dpad, kpad;
+    uint64_t max_chunks;
     uint64_t off_changed, off_cp, off_members, off_table, off_count, off_coff, off_choff, off_part, bytes;
 };
 
@@ -408,14 +306,8 @@ KmeansPlan kmeans_plan(uint64_t n, uint32_t d, uint32_t k) {
     KmeansPlan p;
     p.dpad = (uint32_t)up(d ? d : 1, MK);
     p.kpad = (uint32_t)up(k ? k : 1, MC);
-    p.seg_rows = up((n + USEGS - 1) / USEGS, 64);
-    if (p.seg_rows < USEG_MIN_ROWS) p.seg_rows = USEG_MIN_ROWS;
-    p.segs = (uint32_t)((n + p.seg_rows - 1) / p.seg_rows);
-    if (p.segs < 1) p.segs = 1;
     p.max_chunks = (n + UCHUNK - 1) / UCHUNK + k;            // sum over clusters of ceil(count / UCHUNK) is at most this
-    // the table is sized by a bound on segs that is monotone in n (segs itself is not)
-    const uint64_t by_rows = (n + USEG_MIN_ROWS - 1) / USEG_MIN_ROWS;
-    const uint64_t segs_bound = by_rows < 1 ? 1 : (by_rows < USEGS ? by_rows : USEGS);
+    const uint64_t segs_bound = member_segs(n).segs_bound;
     p.off_changed = up(n * 4, 256);                          // [0, ..): 1 / ||x_r||
     p.off_cp = p.off_changed + 256;
     p.off_members = p.off_cp + up((uint64_t)p.kpad * p.dpad * 4, 256);
@@ -492,11 +384,7 @@ int enqueue_update(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const u
     double *part = reinterpret_cast<double *>(ws + p.off_part);
 
     if (!inv_ready) launch_row_inv_norm(x, ldx, n, n, d, inv, stream);
-    const size_t lds = (size_t)k * 4;
-    hipLaunchKernelGGL(kmeans_count_kernel, dim3(p.segs), dim3(64), lds, stream, labels, n, p.seg_rows, k, table);
-    hipLaunchKernelGGL(kmeans_segscan_kernel, dim3((k + 255) / 256), dim3(256), 0, stream, table, p.segs, k, count);
-    hipLaunchKernelGGL(kmeans_offsets_kernel, dim3(1), dim3(256), 0, stream, count, k, coff, choff);
-    hipLaunchKernelGGL(kmeans_place_kernel, dim3(p.segs), dim3(64), lds, stream, labels, n, p.seg_rows, k, table, coff, members);
+    enqueue_member_lists<UCHUNK>(labels, n, k, table, count, coff, choff, members, stream);
     CL_HIP(hipGetLastError());
     dim3 grid = grid_1d_as_2d(p.max_chunks);
     grid.z = (d + USLAB - 1) / USLAB;

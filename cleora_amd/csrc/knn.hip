@@ -40,6 +40,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "knn_select.h"
 #include "row_inv_norm.h"
 
 namespace cleora {
@@ -50,15 +51,12 @@ constexpr int KC = 128;           // candidate rows per tile
 constexpr int KK = 32;            // columns per staged chunk
 constexpr int KS = KK + 4;        // LDS row stride of a staged chunk (floats)
 constexpr int KD = 256;           // widest padded d whose query tile stays resident
-constexpr int KCAP = 96;          // entries of a query's survivor buffer
 constexpr int KSTEP = 32;         // most entries one selection step can add to a query
 constexpr int KTHREADS = 512;
-constexpr uint32_t KMAXSPLIT = 64;
 constexpr uint32_t KTARGET_BLOCKS = 512;     // two blocks per CU
 constexpr uint32_t KSPLIT_MIN_TILES = 8;     // a split walks at least this many candidate tiles
 constexpr uint32_t kKnnMaxD = 16384;
 constexpr uint64_t kKnnMaxQueries = 1ull << 29;   // query tiles x 512 threads must fit the dispatch's 32-bit x extent
-constexpr uint32_t kNoRow = 0xffffffffu;
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -88,6 +86,27 @@ __global__ __launch_bounds__(64) void knn_pack_kernel(const float *__restrict__ 
     if (lane == 0) qrow[j] = (uint32_t)r;
 }
 
+// The same slots from DENSE query rows (ivf.hip's probe selection): qn[j] = queries[j] / max(||queries[j]||, 1e-10); qrow[j] = j,
+// which only tells the slot from padding (the caller runs without exclude_self).
+__global__ __launch_bounds__(64) void knn_pack_dense_kernel(const float *__restrict__ queries, uint64_t ldq, uint32_t d, uint32_t dpad,
+                                                            uint64_t nq, uint64_t nq_pad, float *__restrict__ qn, uint32_t *__restrict__ qrow) {
+    const uint64_t j = CLEORA_LINEAR_BLOCK();
+    const uint32_t lane = threadIdx.x;
+    if (j >= nq_pad) return;
+    float *out = qn + j * dpad;
+    if (j >= nq) {
+        for (uint32_t c = lane; c < dpad; c += 64) out[c] = 0.0f;
+        if (lane == 0) qrow[j] = kNoRow;
+        return;
+    }
+    const float *xq = queries + j * ldq;
+    float sq = 0.f;
+    for (uint32_t c = lane; c < d; c += 64) sq += xq[c] * xq[c];
+    const float inv = 1.0f / fmaxf(sqrtf(wsum(sq)), 1e-10f);
+    for (uint32_t c = lane; c < dpad; c += 64) out[c] = c < d ? xq[c] * inv : 0.0f;
+    if (lane == 0) qrow[j] = (uint32_t)j;
+}
+
 struct KnnArgs {
     const float *x;
     uint64_t ldx, n;
@@ -102,50 +121,6 @@ struct KnnArgs {
     float *out_score;          // [nq][splits][k]
     uint32_t *out_index;
 };
-
-// One wave: the buffer of query slot q down to its k best, in order.  s / ix: the query's KCAP entries, c of them live, the first
-// `tested` of them already through the edge test.  Returns the new count.
-__device__ __forceinline__ uint32_t knn_compact(float *s, uint32_t *ix, uint32_t c, uint32_t tested, uint32_t k, uint32_t qr,
-                                                const uint64_t *__restrict__ rowptr, const uint32_t *__restrict__ col, float *tau_q,
-                                                int lane) {
-    if (rowptr != nullptr && tested < c) {
-        // (q, r) stored: row q once, a lane per column, against every new entry
-        const uint64_t qb = rowptr[qr], qe = rowptr[qr + 1];
-        for (uint64_t p = qb; p < qe; p += 64) {
-            const uint32_t cv = p + lane < qe ? col[p + lane] : kNoRow;
-            for (uint32_t e = tested; e < c; ++e)
-                if (ix[e] == cv) s[e] = -2.0f;
-        }
-        // (r, q) stored: row r, per entry
-        for (uint32_t e = tested; e < c; ++e) {
-            const uint32_t r = ix[e];
-            const uint64_t rb = rowptr[r], re = rowptr[r + 1];
-            bool found = false;
-            for (uint64_t p = rb; p < re && !found; p += 64) found = __any(p + lane < re && col[p + lane] == qr);
-            if (found && lane == 0) s[e] = -2.0f;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    const bool live0 = (uint32_t)lane < c, live1 = (uint32_t)lane + 64 < c;
-    const float s0 = live0 ? s[lane] : 0.f, s1 = live1 ? s[lane + 64] : 0.f;
-    const uint32_t i0 = live0 ? ix[lane] : 0u, i1 = live1 ? ix[lane + 64] : 0u;
-    uint32_t r0 = 0, r1 = 0;                         // how many entries come before this one: larger score, or equal and larger row
-    for (uint32_t e = 0; e < c; ++e) {
-        const float se = s[e];
-        const uint32_t ie = ix[e];
-        r0 += (se > s0 || (se == s0 && ie > i0)) ? 1u : 0u;
-        r1 += (se > s1 || (se == s1 && ie > i1)) ? 1u : 0u;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (live0 && r0 < k) { s[r0] = s0; ix[r0] = i0; }
-    if (live1 && r1 < k) { s[r1] = s1; ix[r1] = i1; }
-    if (c >= k) {
-        if (live0 && r0 == k - 1) *tau_q = s0;
-        if (live1 && r1 == k - 1) *tau_q = s1;
-    }
-    __builtin_amdgcn_wave_barrier();
-    return c < k ? c : k;
-}
 
 template <bool RESIDENT, bool VEC>
 __global__ __launch_bounds__(KTHREADS) void knn_kernel(const KnnArgs a) {
@@ -294,43 +269,6 @@ __global__ __launch_bounds__(KTHREADS) void knn_kernel(const KnnArgs a) {
     }
 }
 
-// One wave per query: the k best of its splits x k partial entries, descending, ties -> larger row; -inf entries are padding.
-__global__ __launch_bounds__(64) void knn_merge_kernel(const float *__restrict__ part_score, const uint32_t *__restrict__ part_index,
-                                                       uint64_t nq, uint32_t splits, uint32_t k, float *__restrict__ out_score,
-                                                       uint32_t *__restrict__ out_index) {
-    __shared__ float ms[KMAXSPLIT * CLEORA_KNN_MAX_K];
-    __shared__ uint32_t mi[KMAXSPLIT * CLEORA_KNN_MAX_K];
-    const uint64_t qi = CLEORA_LINEAR_BLOCK();
-    if (qi >= nq) return;
-    const uint32_t lane = threadIdx.x, len = splits * k;
-    for (uint32_t e = lane; e < len; e += 64) {
-        ms[e] = part_score[qi * len + e];
-        mi[e] = part_index[qi * len + e];
-    }
-    __syncthreads();
-    for (uint32_t round = 0; round < k; ++round) {
-        float bv = -INFINITY;
-        uint32_t bid = 0, bp = kNoRow;
-        for (uint32_t e = lane; e < len; e += 64) {
-            const float v = ms[e];
-            const uint32_t id = mi[e];
-            if (v > -INFINITY && (bp == kNoRow || v > bv || (v == bv && id > bid))) { bv = v; bid = id; bp = e; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const uint32_t oid = (uint32_t)__shfl_xor((int)bid, o, 64), op = (uint32_t)__shfl_xor((int)bp, o, 64);
-            if (op != kNoRow && (bp == kNoRow || ov > bv || (ov == bv && oid > bid))) { bv = ov; bid = oid; bp = op; }
-        }
-        if (lane == 0) {
-            out_score[qi * k + round] = bv;
-            out_index[qi * k + round] = bid;
-            if (bp != kNoRow) ms[bp] = -INFINITY;
-        }
-        __syncthreads();
-    }
-}
-
 struct KnnPlan {
     uint64_t n_pad, nq_pad, qtiles, rows_per_split;
     uint32_t dpad, splits;
@@ -378,6 +316,34 @@ int launch_knn_cosine(const cleora_graph *g, const float *x, uint64_t ldx, uint6
     if (n_queries == 0) return CLEORA_OK;
     const KnnPlan p = knn_plan(n, d, k, n_queries);
     char *ws = static_cast<char *>(workspace);
+    hipLaunchKernelGGL(knn_pack_kernel, grid_1d_as_2d(p.nq_pad), dim3(64), 0, stream, x, ldx, n, d, p.dpad, queries_dev, n_queries, p.nq_pad,
+                       reinterpret_cast<float *>(ws + p.off_qn), reinterpret_cast<uint32_t *>(ws + p.off_qrow));
+    CL_HIP(hipGetLastError());
+    return launch_knn_packed(g, x, ldx, n, d, n_queries, k, exclude_self, exclude_edges, out_index, out_score, workspace, stream);
+}
+
+KnnSlots knn_query_slots(void *workspace, uint64_t n, uint32_t d, uint32_t k, uint64_t n_queries) {
+    const KnnPlan p = knn_plan(n, d, k, n_queries);
+    char *ws = static_cast<char *>(workspace);
+    return KnnSlots{reinterpret_cast<float *>(ws + p.off_qn), reinterpret_cast<uint32_t *>(ws + p.off_qrow), p.dpad, p.nq_pad};
+}
+
+int launch_knn_pack(const float *src, uint64_t lds, uint64_t n_src, uint32_t d, const uint32_t *rows_dev, uint64_t n_queries,
+                    const KnnSlots &slots, hipStream_t stream) {
+    if (rows_dev != nullptr)
+        hipLaunchKernelGGL(knn_pack_kernel, grid_1d_as_2d(slots.nq_pad), dim3(64), 0, stream, src, lds, n_src, d, slots.dpad, rows_dev,
+                           n_queries, slots.nq_pad, slots.qn, slots.qrow);
+    else
+        hipLaunchKernelGGL(knn_pack_dense_kernel, grid_1d_as_2d(slots.nq_pad), dim3(64), 0, stream, src, lds, d, slots.dpad, n_queries,
+                           slots.nq_pad, slots.qn, slots.qrow);
+    CL_HIP(hipGetLastError());
+    return CLEORA_OK;
+}
+
+int launch_knn_packed(const cleora_graph *g, const float *x, uint64_t ldx, uint64_t n, uint32_t d, uint64_t n_queries, uint32_t k,
+                      int exclude_self, int exclude_edges, uint32_t *out_index, float *out_score, void *workspace, hipStream_t stream) {
+    const KnnPlan p = knn_plan(n, d, k, n_queries);
+    char *ws = static_cast<char *>(workspace);
     float *inv = reinterpret_cast<float *>(ws);
     uint32_t *qrow = reinterpret_cast<uint32_t *>(ws + p.off_qrow);
     float *qn = reinterpret_cast<float *>(ws + p.off_qn);
@@ -385,8 +351,6 @@ int launch_knn_cosine(const cleora_graph *g, const float *x, uint64_t ldx, uint6
     uint32_t *part_index = reinterpret_cast<uint32_t *>(part_score + n_queries * p.splits * k);
 
     launch_row_inv_norm(x, ldx, n, p.n_pad, d, inv, stream);
-    hipLaunchKernelGGL(knn_pack_kernel, grid_1d_as_2d(p.nq_pad), dim3(64), 0, stream, x, ldx, n, d, p.dpad, queries_dev, n_queries,
-                       p.nq_pad, qn, qrow);
     CL_HIP(hipGetLastError());
 
     KnnArgs a;
@@ -422,7 +386,7 @@ int launch_knn_cosine(const cleora_graph *g, const float *x, uint64_t ldx, uint6
     CL_HIP(hipGetLastError());
     if (p.splits > 1) {
         hipLaunchKernelGGL(knn_merge_kernel, grid_1d_as_2d(n_queries), dim3(64), 0, stream, part_score, part_index, n_queries, p.splits, k,
-                           out_score, out_index);
+                           0u, out_score, out_index);
         CL_HIP(hipGetLastError());
     }
     return CLEORA_OK;

@@ -695,6 +695,44 @@ int cleora_kmeans_update_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t 
 int cleora_kmeans_cosine(const float *x_dev, uint64_t ldx, uint64_t n, uint32_t d, float *centroids_io_dev, uint32_t k,
                          uint32_t max_iterations, uint32_t *labels_out_dev, uint32_t *iterations_out, void *workspace, void *stream);
 
+/* Approximate cosine kNN through an inverted-file (IVF) index (csrc/ivf.hip): what pycleora/search.py's ANNIndex is for.  The rows
+ * are grouped into nlist lists by a coarse quantiser — labels and unit centroids, e.g. from cleora_kmeans_* above — and a query is
+ * answered from the lists of its nprobe nearest centroids only.
+ *   build: list_rows_out_dev (u32[n]; the first list_ptr[nlist] entries are written) holds every list's rows in ascending row
+ *   order, list after list; list_ptr_out_dev (u64[nlist + 1]) their offsets.  xs_out_dev (cleora_ivf_xs_bytes(n, d, nlist) BYTES,
+ *   16-byte aligned) is a copy of the rows in list order, each scaled by 1 / max(||x_r||, 1e-10) in f32 and zero-padded to a multiple
+ *   of 32 columns; every list starts on a tile of 128 rows and its last tile is filled with zero rows, so the search fetches whole
+ *   tiles.  A label >= nlist belongs to no list: such a row is never returned.  workspace: cleora_ivf_build_workspace(n, nlist) BYTES.
+ *   search: for every query the top k over the UNION of the lists of its nprobe centroids of highest cosine, [n_queries][k], score
+ *   descending, ties to the larger ORIGINAL row index — the order of cleora_knn_cosine_dev; slots beyond the union's size hold
+ *   index 0xffffffff and score -inf.  Queries are either queries_dev ([n_queries][d] floats, dense; scaled by 1 / max(||q||, 1e-10)
+ *   here) or query_rows_dev (n_queries row indices into x, any order, repeats allowed; then x / ldx are read and exclude_self != 0
+ *   makes a query's own row score -2, which only appears when the union holds fewer than k others) — exactly one of the two; x may be
+ *   NULL with queries_dev.  probes_out_dev (u32[n_queries][nprobe] or NULL): the lists every query probed, best first.
+ *   Four stages per batch of queries: the kNN kernel with the centroids as candidates picks the probes; the (query, probe) pairs are
+ *   regrouped by list with a counting sort whose scatter is in ascending (query, probe slot) order; one block per (list, tile of
+ *   <= 64 probing queries) keeps the queries in LDS, streams the list through the f32 matrix cores and selects in the kernel (lists
+ *   are taken longest first; the grid is launched at the bound ceil(pairs / 64) + nlist and surplus blocks exit); one wave per query
+ *   merges its nprobe partial lists.  workspace: cleora_ivf_search_workspace(n, d, nlist, nprobe, k, n_queries) BYTES, monotone in
+ *   every argument, plain host arithmetic; it fixes the batch: min(n_queries rounded up to 64, 131072) queries, whose partial lists
+ *   (batch x nprobe x k x 8 bytes) are its largest part.  workspace_queries: the n_queries the workspace was sized for (0: this
+ *   call's n_queries) — a workspace sized for fewer queries serves any number of them in more batches.
+ *   Same input, same output bits; no floating-point atomics.  NaN or Inf anywhere: unspecified.
+ *   Limits: 2 <= nlist <= min(n, CLEORA_KMEANS_MAX_K), 1 <= nprobe <= min(nlist, 32), 1 <= k <= 32 = CLEORA_KNN_MAX_K, n < 2^32,
+ *   1 <= d <= 16384, ldx >= d, n_queries < 2^29, exclude_self only with query_rows_dev, no NULL pointer (those named optional
+ *   excepted); anything else returns CLEORA_E_INVALID before any device work.  Stored edges are not masked on this path.
+ * Both *_dev entry points only enqueue on `stream`: nothing is read back, the data-dependent sizes stay on the device. */
+uint64_t cleora_ivf_xs_bytes(uint64_t n, uint32_t d, uint32_t nlist);
+uint64_t cleora_ivf_build_workspace(uint64_t n, uint32_t nlist);
+int cleora_ivf_build_dev(const float *x, uint64_t ldx, uint64_t n, uint32_t d, const uint32_t *labels_dev, uint32_t nlist,
+                         uint64_t *list_ptr_out_dev, uint32_t *list_rows_out_dev, float *xs_out_dev, void *workspace, void *stream);
+uint64_t cleora_ivf_search_workspace(uint64_t n, uint32_t d, uint32_t nlist, uint32_t nprobe, uint32_t k, uint64_t n_queries);
+int cleora_ivf_search_dev(const uint64_t *list_ptr_dev, const uint32_t *list_rows_dev, const float *xs_dev, const float *x, uint64_t ldx,
+                          uint64_t n, uint32_t d, const float *centroids_dev, uint32_t nlist, const float *queries_dev,
+                          const uint32_t *query_rows_dev, uint64_t n_queries, uint32_t nprobe, uint32_t k, int exclude_self,
+                          uint32_t *out_index_dev, float *out_score_dev, uint32_t *probes_out_dev, void *workspace,
+                          uint64_t workspace_queries, void *stream);
+
 /* Product quantisation of an embedding (pycleora/compress.py:32-181, product_quantize / PQIndex) on the device (csrc/pq.hip).  The d
  * columns are cut into n_subspaces slices of d / n_subspaces columns; every slice has its own codebook of n_centroids centroids
  * (codebooks: [n_subspaces][n_centroids][d / n_subspaces] floats, dense) and a row is stored as one byte per slice (codes:
